@@ -344,6 +344,29 @@ int mdt_vae_prologue(const float* z, const float* w, const float* bias, float* y
 /* img[b, c, p] = in[(b, p), c], c < Cout: the decoder output back in the reference's NCHW layout */
 int mdt_vae_epilogue(const float* in, int ld, float* img, int B, int HW, int Cout, mdt_stream_t stream);
 
+/* ---------------------------------------------------------------- VAE encoder glue ------ */
+
+/* The encoder in front of latent extraction (autoencoder.py:212-304 Encoder, :431-434 encode_moments; called by
+ * extract_latent.py).  It reuses the decoder's GroupNorm / implicit-GEMM convolution / attention entries above. */
+/* out[(b, y, x), n] = bias[n] + sum_{ky, kx, c} act[b, 2y + ky, 2x + kx, c] * W[n, (ky * 3 + kx) * C + c], taps on row or
+ * column Hi reading zero: Downsample = F.pad(x, (0, 1, 0, 1)) + nn.Conv2d(C, C, 3, stride = 2, padding = 0)
+ * (autoencoder.py:56-75) as an implicit GEMM; output side Hi / 2.  `act`, W, bias, res, out, gn_sums and every domain
+ * rule (Hi a power of two >= 8, C % 128 == 0, B < 256, B * (Hi/2)^2 % 256 == 0, 32-bit source offsets, THE 256 ZERO BYTES
+ * IN FRONT OF `act`) are those of mdt_conv3x3_nhwc. */
+int mdt_conv3x3_down_nhwc(const mdt_bf16* act, int B, int Hi, int C, const mdt_bf16* W, const float* bias, const float* res,
+                          float* out, int ldo, int Np, float* gn_sums, int gn_groups, mdt_stream_t stream);
+/* col[(b, y, x), (ky * 3 + kx) * 3 + c] = bf16(v[b, c, y + ky - 1, x' + kx - 1]) for columns < 27, zero in the padding
+ * taps and in the columns [27, Kp): conv_in's im2col (autoencoder.py:229-233).  u8 = 0: img is fp32 NCHW [B, 3, R, R]
+ * (encode_moments' argument, in [-1, 1]); u8 = 1: img is uint8 NHWC [B, R, R, 3] and v = (u / 255 - 0.5) / 0.5 in fp32
+ * (ToTensor + Normalize(0.5, 0.5), extract_latent.py:30-33).  flip = 1: v is mirrored in x first (--xflip,
+ * extract_latent.py:91).  Kp % 8 == 0. */
+int mdt_vae_enc_prologue(const void* img, int u8, int flip, mdt_bf16* col, int B, int R, int Kp, mdt_stream_t stream);
+/* moments[b, o, p] = qb[o] + sum_i qw[o, i] * in[(b, p), i], i, o < 8: quant_conv (1x1, 8 -> 8, fp32 weight [8, 8] and
+ * bias) on conv_out's NHWC fp32 result, written as the reference's NCHW fp32 moments [B, 8, H, W] (autoencoder.py:431-434);
+ * ld % 4 == 0. */
+int mdt_vae_enc_epilogue(const float* in, int ld, const float* qw, const float* qb, float* moments, int B, int HW,
+                         mdt_stream_t stream);
+
 /* hipGraph helpers (stream capture of a sequence of the calls above). */
 int mdt_graph_begin(mdt_stream_t stream);
 int mdt_graph_end(mdt_stream_t stream, void** graph_exec_out);

@@ -91,6 +91,9 @@ _PROTOS = {
     'mdt_softmax_rows': [vp, vp, i32, i32, f32],
     'mdt_vae_prologue': [vp, vp, vp, vp, i32, i32, f32],
     'mdt_vae_epilogue': [vp, i32, vp, i32, i32, i32],
+    'mdt_conv3x3_down_nhwc': [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32],
+    'mdt_vae_enc_prologue': [vp, i32, i32, vp, i32, i32, i32],
+    'mdt_vae_enc_epilogue': [vp, i32, vp, vp, vp, i32, i32],
     'mdt_lds_poison': [vp],
     'mdt_gemm_f32': [C.POINTER(GemmF32Args)],
     'mdt_softmax_rows_f32': [vp, i64, i32, i32, f32],

@@ -6,7 +6,7 @@
 
 Parameters carry the reference's state-dict names and shapes (`decoder.mid.block_1.conv1.weight` [512, 512, 3, 3], ...),
 so the published `autoencoder_kl.pth` loads with `load_state_dict` (its `encoder.*` / `quant_conv.*` entries are
-accepted and ignored: encoding is outside the sampling path -- training consumes pre-computed latents).
+accepted and ignored unless the model is built with `encoder=True`, see ENCODE side below).
 
 Arithmetic (maskdit_amd/csrc/vae.hip + the bf16 MFMA GEMMs): activations NHWC fp32; `mdt_gn_im2col` applies GroupNorm(32,
 eps 1e-6) + swish and writes the bf16 operand; every 3x3 convolution with a multiple of 128 input channels is ONE implicit
@@ -18,7 +18,15 @@ CPU fallback.  Supported latent sides: 16, 32, 48, 64 (decode() raises for other
 convolution epilogue (default) the next GroupNorm's statistics are accumulated with fp32 atomics across waves, so two decodes of
 the same latents can differ in the last bits; MDT_VAE_FUSE=0 selects the separate mdt_gn_stats pass, which is run-to-run
 bitwise reproducible (use it where that matters, e.g. FID bookkeeping across runs).  ddconfig is the reference's (ch 128, ch_mult (1, 2, 4, 4), 2 res blocks, no attention resolutions,
-z_channels 4, 3 output channels)."""
+z_channels 4, 3 output channels).
+
+ENCODE side (opt-in: `get_model(path, encoder=True)`): `encode_moments(x)` / `encode(x)` / `forward(x, fn)` of
+autoencoder.py:431-463 -- image [B, 3, R, R] fp32 in [-1, 1] (or uint8 [B, R, R, 3], what extract_latent.py feeds) ->
+moments [B, 8, R/8, R/8] fp32, for R = 128, 256, 512.  The Encoder (:212-304) runs on the decoder's building blocks
+(GroupNorm + swish writer, implicit-GEMM 3x3 convolutions with the fused epilogue, 1x1 GEMMs, the mid-block attention)
+plus three entries of its own: mdt_vae_enc_prologue (image -> conv_in's im2col, optional x mirror),
+mdt_conv3x3_down_nhwc (Downsample: pad (0, 1, 0, 1) + stride-2 convolution) and mdt_vae_enc_epilogue (quant_conv ->
+NCHW moments).  bf16 operands, fp32 accumulation, like decode."""
 from __future__ import annotations
 
 import os
@@ -31,6 +39,8 @@ from . import _lib, ops
 from ._lib import call
 
 CH, CH_MULT, NUM_RES_BLOCKS, Z_CH, OUT_CH, GROUPS = 128, (1, 2, 4, 4), 2, 4, 3, 32
+IN_CH = 3                     # encoder input channels (RGB)
+ENC_SIDES = (128, 256, 512)   # image sides encode_moments accepts
 FUSE_EPILOGUE = os.environ.get('MDT_VAE_FUSE', '1') != '0'  # A/B switch (see _conv)
 # widest convolution (output channels) that takes the fused epilogue: it exists for 128-column tiles only (the 256-wide
 # kernel spills with it), so for 256 / 512 channels fusing trades a ~15-20 % slower GEMM against the saved passes
@@ -82,19 +92,60 @@ def decoder_param_table() -> List[Tuple[str, tuple]]:
     return [('post_quant_conv.weight', (Z_CH, Z_CH, 1, 1)), ('post_quant_conv.bias', (Z_CH,))] + t
 
 
+def encoder_param_table() -> List[Tuple[str, tuple]]:
+    """(state-dict key, shape) of encoder + quant_conv, in the reference's registration order (autoencoder.py:212-284,
+    417-418; double_z: conv_out and quant_conv carry 2 * z_channels = 8 channels)."""
+    t: List[Tuple[str, tuple]] = []
+
+    def conv(name, cin, cout, k):
+        t.extend([(f'{name}.weight', (cout, cin, k, k)), (f'{name}.bias', (cout,))])
+
+    def norm(name, c):
+        t.extend([(f'{name}.weight', (c,)), (f'{name}.bias', (c,))])
+
+    def res(name, cin, cout):
+        norm(f'{name}.norm1', cin)
+        conv(f'{name}.conv1', cin, cout, 3)
+        norm(f'{name}.norm2', cout)
+        conv(f'{name}.conv2', cout, cout, 3)
+        if cin != cout:
+            conv(f'{name}.nin_shortcut', cin, cout, 1)
+
+    conv('encoder.conv_in', IN_CH, CH, 3)
+    block_in = CH
+    for i_level in range(len(CH_MULT)):
+        block_out = CH * CH_MULT[i_level]
+        for j in range(NUM_RES_BLOCKS):
+            res(f'encoder.down.{i_level}.block.{j}', block_in, block_out)
+            block_in = block_out
+        if i_level != len(CH_MULT) - 1:
+            conv(f'encoder.down.{i_level}.downsample.conv', block_in, block_in, 3)
+    res('encoder.mid.block_1', block_in, block_in)
+    norm('encoder.mid.attn_1.norm', block_in)
+    for n in ('q', 'k', 'v', 'proj_out'):
+        conv(f'encoder.mid.attn_1.{n}', block_in, block_in, 1)
+    res('encoder.mid.block_2', block_in, block_in)
+    norm('encoder.norm_out', block_in)
+    conv('encoder.conv_out', block_in, 2 * Z_CH, 3)
+    conv('quant_conv', 2 * Z_CH, 2 * Z_CH, 1)
+    return t
+
+
 def _rup(x, m):
     return (x + m - 1) // m * m
 
 
 class FrozenAutoencoderKL(nn.Module):
-    """Decode-only counterpart of autoencoder.py:412-466."""
+    """Counterpart of autoencoder.py:412-466: decode-only by default; `encoder=True` adds the encoder + quant_conv
+    weights (all of autoencoder_kl.pth, loaded strictly) and the encode side."""
 
-    def __init__(self, pretrained_path: Optional[str] = None, scale_factor: float = 0.18215):
+    def __init__(self, pretrained_path: Optional[str] = None, scale_factor: float = 0.18215, encoder: bool = False):
         super().__init__()
         self.scale_factor = scale_factor
         self.embed_dim = Z_CH
+        self.has_encoder = bool(encoder)
         self._names: List[str] = []
-        for name, shp in decoder_param_table():
+        for name, shp in (encoder_param_table() if encoder else []) + decoder_param_table():
             p = nn.Parameter(torch.zeros(shp), requires_grad=False)
             self.register_parameter(name.replace('.', '__'), p)  # flat registration, reference names restored below
             self._names.append(name)
@@ -115,11 +166,12 @@ class FrozenAutoencoderKL(nn.Module):
         return {name: p.detach() for name, p in self.named_weights()}
 
     def load_state_dict(self, sd, strict: bool = True):
-        """Accepts the full reference checkpoint: `encoder.*` / `quant_conv.*` are not part of the decode path and are
-        skipped; every decode-side key must be present (strict) with the reference shape."""
+        """Accepts the full reference checkpoint: without the encoder, `encoder.*` / `quant_conv.*` are not part of the
+        decode path and are skipped; every key of the model must be present (strict) with the reference shape."""
         own = dict(self.named_weights())
         missing = [k for k in own if k not in sd]
-        unexpected = [k for k in sd if k not in own and not k.startswith(('encoder.', 'quant_conv.'))]
+        skip = () if self.has_encoder else ('encoder.', 'quant_conv.')
+        unexpected = [k for k in sd if k not in own and not (skip and k.startswith(skip))]
         if strict and (missing or unexpected):
             raise RuntimeError(f'autoencoder state dict: missing {missing[:4]}... unexpected {unexpected[:4]}...')
         with torch.no_grad():
@@ -158,11 +210,11 @@ class FrozenAutoencoderKL(nn.Module):
                 b[:cout] = W[base + '.bias'].detach()
                 pk[base] = (m.to(torch.bfloat16).contiguous(), b, Kp, Np)
                 self._cout[base] = cout
-        a = 'decoder.mid.attn_1'
-        wp = W[a + '.proj_out.weight'].detach().reshape(W[a + '.proj_out.weight'].shape[0], -1)
-        beff = W[a + '.proj_out.bias'].detach() + wp @ W[a + '.v.bias'].detach()
-        m, _, Kp, Np = pk[a + '.proj_out']
-        pk[a + '.proj_out'] = (m, beff.contiguous(), Kp, Np)
+        for a in ('decoder.mid.attn_1', 'encoder.mid.attn_1') if self.has_encoder else ('decoder.mid.attn_1',):
+            wp = W[a + '.proj_out.weight'].detach().reshape(W[a + '.proj_out.weight'].shape[0], -1)
+            beff = W[a + '.proj_out.bias'].detach() + wp @ W[a + '.v.bias'].detach()
+            m, _, Kp, Np = pk[a + '.proj_out']
+            pk[a + '.proj_out'] = (m, beff.contiguous(), Kp, Np)
         self._packed = pk
         return pk
 
@@ -183,8 +235,10 @@ class FrozenAutoencoderKL(nn.Module):
         return t[:n].view(shape)
 
     # ---- building blocks -----------------------------------------------------------------------
-    def _conv(self, x, B, H, cin, name, k=3, norm=None, swish=False, up=0, slot='a', in_stats=None, res=None, want_stats=False):
-        """x: fp32 [B*H*H, cin] (NHWC) -> (fp32 [B*Ho*Ho, Np], stats).  `in_stats`: GroupNorm sums of x that the
+    def _conv(self, x, B, H, cin, name, k=3, norm=None, swish=False, up=0, slot='a', in_stats=None, res=None, want_stats=False,
+              down=0):
+        """x: fp32 [B*H*H, cin] (NHWC) -> (fp32 [B*Ho*Ho, Np], stats).  `down`: the encoder's Downsample (pad (0, 1, 0, 1),
+        stride 2, Ho = H / 2; implicit-GEMM form only).  `in_stats`: GroupNorm sums of x that the
         PRODUCER of x already accumulated (round 4: the implicit-GEMM convolution's epilogue), else mdt_gn_stats runs;
         `res`: fp32 [B*Ho*Ho, Np] added to the result inside the epilogue where the implicit-GEMM kernel runs (else by
         mdt_add_f32); `want_stats`: return the sums [B, 32, 2] of the result when the epilogue can produce them."""
@@ -198,7 +252,7 @@ class FrozenAutoencoderKL(nn.Module):
                 sums = self._buf('sums', (B, GROUPS, 2), torch.float32)
                 call('mdt_gn_stats', x.data_ptr(), sums.data_ptr(), B, H * H, cin, GROUPS, st)
             gamma, beta = W[norm + '.weight'], W[norm + '.bias']
-        Ho = H << up
+        Ho = H >> 1 if down else H << up
         M = B * Ho * Ho
         # the implicit-GEMM kernel's shape domain (mdt_conv3x3_nhwc): power-of-two image sides >= 8, whole 256-row tiles,
         # 8-bit batch index, 32-bit source offsets; anything else inside decode()'s domain (R = 48 latents: 48, 96, 192, 384
@@ -208,6 +262,9 @@ class FrozenAutoencoderKL(nn.Module):
         # size-agnostic, this one covers the sides the shipped configs (32, 64) and their neighbours use
         implicit_ok = (k == 3 and cin % 128 == 0 and H >= 8 and (H & (H - 1)) == 0 and M % 256 == 0 and B < 256
                        and Ho <= 2048 and B * H * H * cin * 2 + 256 < (1 << 32))
+        if down and not implicit_ok:
+            raise NotImplementedError(f'maskdit_amd.autoencoder: stride-2 convolution outside the implicit-GEMM domain '
+                                      f'(B {B}, H {H}, C {cin}): encode_moments chunks the batch to stay inside it')
         if implicit_ok:
             # implicit GEMM (round 3): the normalised activation is written ONCE as bf16 NHWC (ksize-1 form of
             # mdt_gn_im2col) behind a 256-byte zero line, the MFMA kernel gathers the nine taps (and the 2x up-sampling)
@@ -231,9 +288,14 @@ class FrozenAutoencoderKL(nn.Module):
                 stats = self._buf('sums_' + slot, (B, GROUPS, 2), torch.float32)
                 stats.zero_()
             fres = res if fuse else None
-            call('mdt_conv3x3_nhwc', act.data_ptr(), B, H, cin, up, wmat.data_ptr(), bias.data_ptr(),
-                 fres.data_ptr() if fres is not None else None, out.data_ptr(), Np, Np,
-                 stats.data_ptr() if stats is not None else None, GROUPS, st)
+            if down:
+                call('mdt_conv3x3_down_nhwc', act.data_ptr(), B, H, cin, wmat.data_ptr(), bias.data_ptr(),
+                     fres.data_ptr() if fres is not None else None, out.data_ptr(), Np, Np,
+                     stats.data_ptr() if stats is not None else None, GROUPS, st)
+            else:
+                call('mdt_conv3x3_nhwc', act.data_ptr(), B, H, cin, up, wmat.data_ptr(), bias.data_ptr(),
+                     fres.data_ptr() if fres is not None else None, out.data_ptr(), Np, Np,
+                     stats.data_ptr() if stats is not None else None, GROUPS, st)
             if res is not None and fres is None:
                 out = self._add(res, out, slot)
             return out, stats
@@ -334,20 +396,121 @@ class FrozenAutoencoderKL(nn.Module):
         call('mdt_vae_epilogue', y.data_ptr(), y.shape[1], img.data_ptr(), B, H * H, OUT_CH, st)
         return img
 
-    def encode(self, x):
-        raise NotImplementedError('encoding (autoencoder.py:203-304) is outside the sampling path: training consumes '
-                                  'pre-computed latent moments (train_utils/datasets.py:240-304)')
+    @staticmethod
+    def encode_chunk(R: int) -> int:
+        """Images per launch sequence of encode_moments: the largest power of two <= 64 that keeps the widest activation
+        (R x R x 128 bf16 per image) inside the implicit-GEMM convolution's 32-bit source offsets (512^2: 32)."""
+        n = 64
+        while n > 1 and n * R * R * CH * 2 + 256 >= (1 << 32):
+            n //= 2
+        return n
+
+    @torch.no_grad()
+    def encode_moments(self, x: torch.Tensor, flip: bool = False) -> torch.Tensor:
+        """autoencoder.py:431-434: Encoder -> quant_conv.  x: fp32 [B, 3, R, R] in [-1, 1] (the reference's argument), or
+        uint8 [B, R, R, 3] (an RGB batch as PIL decodes it; ToTensor + Normalize(0.5, 0.5) applied in the prologue).
+        flip: mirror the images in x first (extract_latent.py --xflip).  -> moments fp32 [B, 8, R/8, R/8]."""
+        if not self.has_encoder:
+            raise NotImplementedError('maskdit_amd.autoencoder: this model was built without the encoder '
+                                      '(get_model(path, encoder=True) loads it)')
+        if not x.is_cuda:
+            raise _lib.MaskDiTLibError('maskdit_amd.autoencoder: x is not on a HIP device; there is no CPU path')
+        if next(self.parameters()).device != x.device:
+            raise _lib.MaskDiTLibError('maskdit_amd.autoencoder: call .to(x.device) first')
+        u8 = x.dtype == torch.uint8
+        if u8:
+            assert x.dim() == 4 and x.shape[3] == IN_CH, f'uint8 images are [B, R, R, 3], got {tuple(x.shape)}'
+            B, R, R2 = x.shape[:3]
+        else:
+            assert x.dim() == 4 and x.shape[1] == IN_CH, f'images are [B, 3, R, R], got {tuple(x.shape)}'
+            B, R, R2 = x.shape[0], x.shape[2], x.shape[3]
+            x = x.to(torch.float32)
+        if R != R2 or R not in ENC_SIDES:
+            # the mid-block attention runs on (R/8)^2 tokens (softmax rows <= 4096: R <= 512) and every convolution is an
+            # implicit GEMM on power-of-two sides; 384 (and any other side) is outside what this encoder covers
+            raise NotImplementedError(f'maskdit_amd.autoencoder: image side {R}x{R2} unsupported (square, one of {ENC_SIDES})')
+        x = x.contiguous()
+        if self._packed is None:
+            self._pack()
+        mom = torch.empty(B, 2 * Z_CH, R // 8, R // 8, device=x.device, dtype=torch.float32)
+        n = self.encode_chunk(R)
+        for s in range(0, B, n):
+            self._encode_chunk(x[s:s + n], u8, flip, mom[s:s + n])
+        return mom
+
+    def _encode_chunk(self, x, u8, flip, mom):
+        st = ops.stream_ptr()
+        W = self._weights()
+        B = x.shape[0]
+        R = x.shape[1] if u8 else x.shape[2]
+        wmat, bias, Kp, Np = self._packed['encoder.conv_in']
+        col = self._buf('col', (B * R * R, Kp), torch.bfloat16)
+        call('mdt_vae_enc_prologue', x.data_ptr(), int(u8), int(bool(flip)), col.data_ptr(), B, R, Kp, st)
+        h = self._buf('out_x1', (B * R * R, Np), torch.float32)
+        ops.gemm_nt(col, wmat, bias, ops.EPI_F32, outf=h)
+        H, c, xs, sl = R, CH, None, 0
+        for i_level in range(len(CH_MULT)):
+            cout = CH * CH_MULT[i_level]
+            for j in range(NUM_RES_BLOCKS):
+                h, xs = self._res(h, B, H, c, cout, f'encoder.down.{i_level}.block.{j}', 'pq'[sl], xs)
+                sl ^= 1
+                c = cout
+            if i_level != len(CH_MULT) - 1:
+                h, xs = self._conv(h, B, H, c, f'encoder.down.{i_level}.downsample.conv', down=1, slot='u', want_stats=True)
+                H //= 2
+        h, _ = self._res(h, B, H, c, c, 'encoder.mid.block_1', 'pq'[sl], xs)
+        h = self._attn(h, B, H, c, 'encoder.mid.attn_1', 'pq'[sl ^ 1])
+        h, xs = self._res(h, B, H, c, c, 'encoder.mid.block_2', 'pq'[sl])
+        y, _ = self._conv(h, B, H, c, 'encoder.conv_out', norm='encoder.norm_out', swish=True, slot='a', in_stats=xs)
+        call('mdt_vae_enc_epilogue', y.data_ptr(), y.shape[1], W['quant_conv.weight'].data_ptr(), W['quant_conv.bias'].data_ptr(),
+             mom.data_ptr(), B, H * H, st)
+
+    def sample(self, moments: torch.Tensor) -> torch.Tensor:
+        """autoencoder.py:436-442 (== utils.sample): scale_factor * (mean + exp(logvar / 2) * randn), logvar clamped."""
+        from . import latents
+        return latents.sample(moments, self.scale_factor)
+
+    def encode(self, x, flip: bool = False):
+        """autoencoder.py:444-447: sample(encode_moments(x))."""
+        if not self.has_encoder:
+            raise NotImplementedError('encoding (autoencoder.py:203-304) is outside the sampling path: training consumes '
+                                      'pre-computed latent moments (train_utils/datasets.py:240-304); '
+                                      'get_model(path, encoder=True) builds the encoder')
+        return self.sample(self.encode_moments(x, flip=flip))
 
     def forward(self, inputs, fn):
         if fn == 'decode':
             return self.decode(inputs)
-        return self.encode(inputs)
+        if fn == 'encode_moments':
+            return self.encode_moments(inputs)
+        if fn == 'encode':
+            return self.encode(inputs)
+        raise NotImplementedError(fn)
 
     def release_workspace(self):
         self._ws.clear()
         self._act_zeroed = None
 
 
-def get_model(pretrained_path: Optional[str], scale_factor: float = 0.18215) -> FrozenAutoencoderKL:
-    """autoencoder.py:468-474 (`pretrained_path=None`: zero weights, to be filled with load_state_dict)."""
-    return FrozenAutoencoderKL(pretrained_path, scale_factor)
+def synthetic_state_dict(seed: int = 0, encoder: bool = True) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in weights in the checkpoint layout (tools without autoencoder_kl.pth: extract_latent.py --ckpt none,
+    tools/vae_encode_bench.py): convolutions N(0, 1.6 / fan_in) (activations stay O(1) through the ~30 layers), biases
+    N(0, 0.05), GroupNorm gamma 1 + N(0, 0.1), beta N(0, 0.1)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, shp in (encoder_param_table() if encoder else []) + decoder_param_table():
+        if name.endswith('.weight') and len(shp) == 4:
+            sd[name] = torch.randn(shp, generator=g) * (1.6 / (shp[1] * shp[2] * shp[3])) ** 0.5
+        elif '.norm' in name and name.endswith('.weight'):
+            sd[name] = 1.0 + 0.1 * torch.randn(shp, generator=g)
+        elif '.norm' in name:
+            sd[name] = 0.1 * torch.randn(shp, generator=g)
+        else:
+            sd[name] = 0.05 * torch.randn(shp, generator=g)
+    return sd
+
+
+def get_model(pretrained_path: Optional[str], scale_factor: float = 0.18215, encoder: bool = False) -> FrozenAutoencoderKL:
+    """autoencoder.py:468-474 (`pretrained_path=None`: zero weights, to be filled with load_state_dict; `encoder=True`:
+    the encode side as well)."""
+    return FrozenAutoencoderKL(pretrained_path, scale_factor, encoder=encoder)

@@ -12,6 +12,11 @@
 //   mdt_softmax_rows    : the attention block's row softmax (fp32 scores -> bf16 probabilities)
 //   mdt_vae_prologue    : z / scale_factor -> post_quant_conv (1x1, 4 -> 4), NCHW -> NHWC
 //   mdt_vae_epilogue    : NHWC [.., ld] fp32 -> NCHW image [B, C_out, H, W]
+//
+// ... and the ENCODER's two ends (reference autoencoder.py:212-304 Encoder, :431-434 encode_moments):
+//   mdt_vae_enc_prologue: image (fp32 NCHW in [-1, 1], or uint8 NHWC + ToTensor / Normalize(0.5, 0.5)), optionally
+//                         mirrored in x -> the bf16 im2col matrix of conv_in (3x3, padding 1, K = 27 zero-padded to Kp)
+//   mdt_vae_enc_epilogue: conv_out's NHWC fp32 [.., ld] (8 columns) -> quant_conv (1x1, 8 -> 8) -> NCHW moments
 #include "common.h"
 #include "../../include/maskdit_hip.h"
 
@@ -183,6 +188,55 @@ __global__ __launch_bounds__(256) void vae_epilogue_kernel(const float* __restri
   for (int c = 0; c < Cout; ++c) img[((long)b * Cout + c) * HW + p] = in[i * ld + c];
 }
 
+// encoder prologue: one thread = 8 consecutive columns (ky, kx, c) of one output row; column k < 27 is tap k / 3,
+// channel k % 3 of the (mirrored) image at (y + ky - 1, x + kx - 1), zero outside it and in the columns [27, Kp)
+__global__ __launch_bounds__(256) void vae_enc_prologue_kernel(const void* __restrict__ img, int u8, int flip, bf16* __restrict__ col,
+                                                               int B, int R, int Kp) {
+  const int chunks = Kp >> 3;
+  const long total = (long)B * R * R * chunks;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int ch = (int)(idx % chunks);
+  const long row = idx / chunks;
+  const int xo = (int)(row % R), yo = (int)((row / R) % R), b = (int)(row / ((long)R * R));
+  bf16x8 o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int k = ch * 8 + e, tap = k / 3, c = k - tap * 3;
+    const int yy = yo + tap / 3 - 1, xx = xo + tap % 3 - 1;
+    float v = 0.f;
+    if (k < 27 && yy >= 0 && yy < R && xx >= 0 && xx < R) {
+      const int sx = flip ? R - 1 - xx : xx;  // img.flip(dims=[-1]) (extract_latent.py:91)
+      if (u8) {
+        // ToTensor (u / 255) then Normalize(0.5, 0.5) (extract_latent.py:30-33), in fp32 with IEEE-rounded divisions
+        const float u = (float)((const unsigned char*)img)[(((long)b * R + yy) * R + sx) * 3 + c];
+        v = __fdiv_rn(__fdiv_rn(u, 255.f) - 0.5f, 0.5f);
+      } else {
+        v = ((const float*)img)[(((long)b * 3 + c) * R + yy) * R + sx];
+      }
+    }
+    o[e] = f2bf(v);
+  }
+  *(bf16x8*)(col + row * Kp + ch * 8) = o;
+}
+
+// encoder epilogue: moments[b, o, p] = qb[o] + sum_i qw[o, i] h[(b, p), i] (quant_conv, autoencoder.py:421,433)
+__global__ __launch_bounds__(256) void vae_enc_epilogue_kernel(const float* __restrict__ in, int ld, const float* __restrict__ qw,
+                                                               const float* __restrict__ qb, float* __restrict__ mom, int B, int HW) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * HW) return;
+  const int b = (int)(i / HW), p = (int)(i % HW);
+  const f32x4 h0 = *(const f32x4*)(in + i * ld), h1 = *(const f32x4*)(in + i * ld + 4);
+  const float h[8] = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+#pragma unroll
+  for (int o = 0; o < 8; ++o) {
+    float acc = qb[o];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) acc += qw[8 * o + c] * h[c];
+    mom[((long)b * 8 + o) * HW + p] = acc;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 
 extern "C" int mdt_gn_stats(const float* x, float* sums, int B, int HW, int C, int groups, mdt_stream_t stream) {
@@ -234,4 +288,26 @@ extern "C" int mdt_vae_epilogue(const float* in, int ld, float* img, int B, int 
   MDT_REQUIRE(in && img && B > 0 && HW > 0 && Cout > 0 && ld >= Cout, "vae_epilogue: bad arguments");
   hipLaunchKernelGGL(vae_epilogue_kernel, dim3(cdiv((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, in, ld, img, B, HW, Cout);
   return mdt_check_launch("vae_epilogue");
+}
+
+extern "C" int mdt_vae_enc_prologue(const void* img, int u8, int flip, mdt_bf16* col, int B, int R, int Kp, mdt_stream_t stream) {
+  MDT_REQUIRE(img && col, "vae_enc_prologue: null pointer");
+  MDT_REQUIRE((u8 == 0 || u8 == 1) && (flip == 0 || flip == 1), "vae_enc_prologue: u8 and flip are 0 or 1");
+  MDT_REQUIRE(B > 0 && R > 0 && Kp >= 27 && Kp % 8 == 0 && ((uintptr_t)col & 15) == 0,
+              "vae_enc_prologue: B, R > 0, Kp >= 27 and a multiple of 8, col 16-byte aligned");
+  const long total = (long)B * R * R * (Kp / 8);
+  MDT_REQUIRE(total / 256 < 2147483647L, "vae_enc_prologue: problem size");
+  hipLaunchKernelGGL(vae_enc_prologue_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, img, u8, flip,
+                     (bf16*)col, B, R, Kp);
+  return mdt_check_launch("vae_enc_prologue");
+}
+
+extern "C" int mdt_vae_enc_epilogue(const float* in, int ld, const float* qw, const float* qb, float* moments, int B, int HW,
+                                    mdt_stream_t stream) {
+  MDT_REQUIRE(in && qw && qb && moments, "vae_enc_epilogue: null pointer");
+  MDT_REQUIRE(B > 0 && HW > 0 && ld >= 8 && ld % 4 == 0 && ((uintptr_t)in & 15) == 0,
+              "vae_enc_epilogue: B, HW > 0, ld >= 8 and a multiple of 4, in 16-byte aligned");
+  hipLaunchKernelGGL(vae_enc_epilogue_kernel, dim3(cdiv((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, in, ld, qw, qb,
+                     moments, B, HW);
+  return mdt_check_launch("vae_enc_epilogue");
 }

@@ -64,7 +64,7 @@ WATCH = {
     'gemm_nt8_c2.hip': [(r'gemm_nt8_kernel', 'nt8')],
     'gemm_nt8_c3.hip': [(r'gemm_nt8_kernel', 'nt8')],
     'gemm_nt8_c4.hip': [(r'gemm_nt8_kernel', 'nt8')],
-    'gemm_nt8_conv.hip': [(r'gemm_nt8_kernel', 'nt8')],
+    'gemm_nt8_conv.hip': [(r'gemm_nt8_kernel', 'nt8'), (r'gemm_nt8_conv_down_kernel', 'nt8')],
     'gemm_nt8o.hip': [(r'gemm_nt8o_kernel', 'nt8o')],
     'gemm_tn8.hip': [(r'gemm_tn8_kernel', 'tn8')],
     'norm.hip': [(r'ln_bwd_gate_split_kernel', 'generic'), (r'ln_modulate_(fwd|bwd)_kernel', 'generic')],
@@ -477,10 +477,11 @@ def linear_events(kern, names):
 
 def rule_nt8(kern, pretty, entry, rep):
     m = re.search(r'gemm_nt8_kernel<(\d+), (\d+), (\d+)', pretty)
-    if not m:
+    md = re.search(r'gemm_nt8_conv_down_kernel<(\d+), (\d+)', pretty)  # the stride-2 convolution: WR = 2
+    if not m and not md:
         rep.err(pretty, 'cannot read the template arguments')
         return
-    nf, wr = int(m.group(1)), int(m.group(2))
+    nf, wr = (int(m.group(1)), int(m.group(2))) if m else (int(md.group(1)), 2)
     rpp = 2 // wr
     expect = []
     for _half in range(2):
