@@ -55,9 +55,11 @@ def main(argv=None):
     ap.add_argument('--class_idx', type=int, default=None)
     ap.add_argument('--subdirs', action='store_true', help='one sub-directory per 1000 seeds (sample.py:288)')
     ap.add_argument('--pretrained_path', default=None, help='autoencoder_kl.pth: decode the latents to images (sample.py:248)')
-    ap.add_argument('--precision', choices=['bf16', 'fp32'], default='bf16',
+    ap.add_argument('--precision', choices=['bf16', 'fp32', 'bf16x3'], default='bf16',
                     help="arithmetic of the network evaluations: 'fp32' = exact fp32 weights / activations / matrix instructions, what "
-                         "the reference's own sampler runs (sample.py:56; ~1/9 of the bf16 throughput); 'bf16' = the training kernels")
+                         "the reference's own sampler runs (sample.py:56; ~1/9 of the bf16 throughput); 'bf16x3' = the same fp32 "
+                         "network with its Linear layers on the bf16 matrix instruction (every fp32 operand split exactly into three "
+                         "bf16 terms, six cross products summed in fp32: fp32-level accuracy); 'bf16' = the training kernels")
     args = ap.parse_args(argv)
     cfg = load_config(args.config)
     world = int(os.environ.get('WORLD_SIZE', '1'))

@@ -290,6 +290,11 @@ typedef struct {
   long a_stride_b, a_stride_h, b_stride_b, b_stride_h, o_stride_b, o_stride_h;
 } mdt_gemm_f32_args;
 int mdt_gemm_f32(const mdt_gemm_f32_args* a, mdt_stream_t stream);
+/* The same product for the Linear layers (batch <= 1, heads <= 1, b_kmajor = 0) at fp32-level accuracy on the bf16 matrix
+ * instruction: every fp32 operand is split exactly into three bf16 terms and six of the nine cross products are summed in
+ * fp32 (the dropped three are <= ~2^-24 of the product).  Same epilogues; deterministic.  Inference plans of precision
+ * 'bf16x3'. */
+int mdt_gemm_bf16x3(const mdt_gemm_f32_args* a, mdt_stream_t stream);
 /* s[r, :] = softmax(s[r, :n_valid] * scale), in place, columns >= n_valid set to 0 (timm Attention: softmax(q k^T * hd^-0.5)) */
 int mdt_softmax_rows_f32(float* s, long R, int n, int n_valid, float scale, mdt_stream_t stream);
 /* timm Attention (call site models/maskdit.py:178) in exact fp32 on the packed qkv buffer [B*L, 3*H*hd] -> out [B*L, H*hd].

@@ -96,6 +96,7 @@ _PROTOS = {
     'mdt_vae_enc_epilogue': [vp, i32, vp, vp, vp, i32, i32],
     'mdt_lds_poison': [vp],
     'mdt_gemm_f32': [C.POINTER(GemmF32Args)],
+    'mdt_gemm_bf16x3': [C.POINTER(GemmF32Args)],
     'mdt_softmax_rows_f32': [vp, i64, i32, i32, f32],
     'mdt_attn_f32': [vp, vp, vp, i32, i32, i32, i32],
     'mdt_ln_modulate_f32': [vp, vp, vp, i32, i32, vp, i32, i32],

@@ -462,6 +462,216 @@ int launch(const Params& p, bool bkm, int batch, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// bf16x3: the Linear layers' C = A * B^T (+ bias) on fp32 operands at fp32-level accuracy on the bf16 matrix pipe (16x the
+// fp32 one).  Every fp32 x splits EXACTLY into x = b0 + b1 + b2 (three bf16 terms of 8 significand bits each, fp32's
+// exponent range: b0 = rne(x), b1 = rne(x - b0), b2 = x - b0 - b1), and of the nine products of two split operands the six
+// with term indices summing to <= 2 are kept: a c = a0 c0 + (a0 c1 + a1 c0 + a0 c2 + a1 c1 + a2 c0) + O(2^-24 |a c|).  The
+// main product a0 c0 has its own accumulator, so it rounds once per 16-k MFMA instead of once per k (mdt_gemm_f32's fma
+// chain); the five corrections (~2^-8 of it) share a second one; the two are added once before the fp32 epilogue.
+// Structure: 128 x 128 x 32 tile, 8 waves of 64 x 32 (two per SIMD), global loads staged in registers one K-tile ahead; a
+// tile is split ONCE per element while it is written to LDS (three bf16 planes of [256 rows][32 k], 64-byte rows; 2 x 48 KiB
+// double-buffered) and a fragment is one ds_read_b128 per plane.  v_mfma_f32_32x32x16_bf16 takes
+// the B fragment first, as fmma does, so the accumulator layout is the one f32_epilogue consumes.  No atomics, no split-K:
+// repeated runs give identical bits.
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+
+__device__ __forceinline__ unsigned x3_pk(float lo, float hi) {  // two RNE bf16 in one dword (v_cvt_pk_bf16_f32)
+  const bf16x2 h = __builtin_convertvector((f32x2){lo, hi}, bf16x2);
+  return __builtin_bit_cast(unsigned, h);
+}
+__device__ __forceinline__ f32x2 x3_unpk(unsigned w) {
+  return (f32x2){__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+}
+#define X3_INLINE __attribute__((always_inline))  // (the K loop must not become calls)
+__device__ __forceinline__ bool x3_finite(float v) { return fabsf(v) <= 3.4028235e38f; }  // false for inf and NaN
+
+// eight consecutive k of one row -> the same 16 bytes of the three planes.  Not finite x: b1 = b2 = 0 (inf stays inf, NaN
+// stays NaN); a finite x that RNE would round to inf: b0 rounds toward zero.  Both show as a non-finite x - b0.
+__device__ __forceinline__ void x3_split8(const f32x4 v0, const f32x4 v1, u32x4& p0, u32x4& p1, u32x4& p2) {
+  f32x2 x[4] = {(f32x2){v0[0], v0[1]}, (f32x2){v0[2], v0[3]}, (f32x2){v1[0], v1[1]}, (f32x2){v1[2], v1[3]}};
+  unsigned w0[4];
+  f32x2 r[4];
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    w0[j] = x3_pk(x[j][0], x[j][1]);
+    r[j] = x[j] - x3_unpk(w0[j]);
+    bad |= !x3_finite(r[j][0]) || !x3_finite(r[j][1]);
+  }
+  if (__any(bad)) {  // wave-uniform: a branch hipcc keeps, not selects on every element
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        if (x3_finite(r[j][e])) continue;
+        const float xe = x[j][e];
+        if (!x3_finite(xe)) {
+          r[j][e] = 0.f;
+        } else {
+          const unsigned t = __float_as_uint(xe) >> 16;  // toward zero
+          w0[j] = e ? (w0[j] & 0xffffu) | (t << 16) : (w0[j] & 0xffff0000u) | t;
+          r[j][e] = xe - __uint_as_float(t << 16);
+        }
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned w1 = x3_pk(r[j][0], r[j][1]);
+    const f32x2 r2 = r[j] - x3_unpk(w1);
+    p0[j] = w0[j];
+    p1[j] = w1;
+    p2[j] = x3_pk(r2[0], r2[1]);
+  }
+}
+
+__global__ __launch_bounds__(512) void gemm_bf16x3_kernel(const Params p, const int tiles_m, const int tiles_n) {
+  constexpr int NT = 512, WN = 4, MB = 2, NB = 1, BM = 128, BN = 128, BKT = 32;  // 8 waves (2 per SIMD) of 64 x 32
+  constexpr int CPR = BKT / 8;                          // 16-byte chunks (8 k) per LDS row of a plane
+  constexpr int CH = BM * CPR / NT;                     // chunks per thread and K-tile, of A and of B (BM == BN)
+  constexpr int PLANE = (BM + BN) * CPR;                // 16-byte chunks of one plane of one buffer
+  static_assert(CH >= 1 && BM == BN, "tile");
+  __shared__ __attribute__((aligned(16))) u32x4 lds[2][3][PLANE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const int nt = tiles_m * tiles_n;
+  int t = blockIdx.x;
+  {
+    const int q = nt >> 3, r = nt & 7, x = t & 7, i = t >> 3;
+    t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
+  }
+  constexpr int GM = 8;
+  const int per_group = GM * tiles_n, grp = t / per_group, first_m = grp * GM;
+  const int gm = min(tiles_m - first_m, GM), in_g = t - grp * per_group;
+  const int tm = first_m + in_g % gm, tn = in_g / gm;
+  const int m0 = tm * BM, n0 = tn * BN;
+
+  f32x16 acc[MB][NB], cor[MB][NB];
+#pragma unroll
+  for (int i = 0; i < MB; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = cor[i][j][e] = 0.f;
+
+  // thread chunk q = tid + NT i: tile row q / CPR, k = 8 (q % CPR) .. + 7 as two 16-byte global loads; operand o = 0 (A)
+  // / 1 (B).  Rows beyond M / N are clamped to the last row: they only feed output rows / columns that are never stored,
+  // so the loads need no select (which would make the wave wait for them right away).
+  f32x4 g[2][CH][2];
+  const float* pg[2][CH];
+#pragma unroll
+  for (int i = 0; i < CH; ++i) {
+    const int q = tid + NT * i, row = q / CPR, c = q % CPR;
+    pg[0][i] = p.A + (long)min(m0 + row, p.M - 1) * p.lda + 8 * c;
+    pg[1][i] = p.B + (long)min(n0 + row, p.N - 1) * p.ldb + 8 * c;
+  }
+  const bool k_ragged = (p.K % BKT) != 0;
+  auto gload = [&](int k0) X3_INLINE {
+    if (!k_ragged || k0 + BKT <= p.K) {
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+#pragma unroll
+        for (int i = 0; i < CH; ++i)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) g[o][i][h] = *(const f32x4*)(pg[o][i] + k0 + 4 * h);
+    } else {  // last, partial K-tile: the K tail reads as zeros (addresses clamped inside the operand rows)
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+#pragma unroll
+        for (int i = 0; i < CH; ++i)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int c4 = 8 * ((tid + NT * i) % CPR) + 4 * h;
+            const f32x4 v = *(const f32x4*)(pg[o][i] + 4 * h + min(k0, p.K - 4 - c4));
+            g[o][i][h] = k0 + c4 < p.K ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
+          }
+    }
+  };
+  // chunk c of LDS row `row` (A rows 0 .. BM - 1, then B) sits at row * CPR + (c ^ ((row >> 2) & 3)): the 16 consecutive
+  // rows of a fragment read's lane group land on 16 distinct 16-byte bank slots
+  auto lstore = [&](int buf) X3_INLINE {
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int i = 0; i < CH; ++i) {
+        const int q = tid + NT * i, row = q / CPR + o * BM, c = q % CPR;
+        const int at = row * CPR + (c ^ ((row >> 2) & 3));
+        u32x4 w0, w1, w2;
+        x3_split8(g[o][i][0], g[o][i][1], w0, w1, w2);
+        lds[buf][0][at] = w0;
+        lds[buf][1][at] = w1;
+        lds[buf][2][at] = w2;
+      }
+  };
+
+  const int nk = (p.K + BKT - 1) / BKT;
+  const int r = lane & 31, kh = lane >> 5;
+  // fragments of k-step s (16 k) of the three planes: lane (r, kh) holds row r, k = 16 s + 8 kh .. + 7
+  bf16x8 fa[3][MB], fb[3][NB];
+  auto fload = [&](int buf, int s) X3_INLINE {
+#pragma unroll
+    for (int i = 0; i < MB; ++i) {
+      const int row = (wm * MB + i) * 32 + r;
+      const int at = row * CPR + ((2 * s + kh) ^ ((row >> 2) & 3));
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) fa[pl][i] = __builtin_bit_cast(bf16x8, lds[buf][pl][at]);
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int row = BM + (wn * NB + i) * 32 + r;
+      const int at = row * CPR + ((2 * s + kh) ^ ((row >> 2) & 3));
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) fb[pl][i] = __builtin_bit_cast(bf16x8, lds[buf][pl][at]);
+    }
+  };
+  // six products per block and k-step; consecutive MFMAs go to different accumulators
+  auto fmma = [&]() X3_INLINE {
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+      for (int jj = 0; jj < NB; ++jj) acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[0][jj], fa[0][i], acc[i][jj], 0, 0, 0);
+    constexpr int PB[5] = {0, 1, 0, 1, 2}, PA[5] = {1, 0, 2, 1, 0};  // (B plane, A plane) of the corrections
+#pragma unroll
+    for (int pr = 0; pr < 5; ++pr)
+#pragma unroll
+      for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int jj = 0; jj < NB; ++jj)
+          cor[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[PB[pr]][jj], fa[PA[pr]][i], cor[i][jj], 0, 0, 0);
+  };
+  // K-tile kt (buffer kt & 1): the loads of tile kt + 1 are issued at the top and split into the other buffer after the
+  // MFMAs -- that buffer held tile kt - 1, whose reads completed before the previous barrier (hipcc counts the waits).
+  // Two waves per SIMD: one wave's split (VALU) and stores run under the other's MFMAs.
+  auto step = [&](auto par_c, int kt) X3_INLINE {
+    constexpr int par = decltype(par_c)::value;
+    const bool more = kt + 1 < nk;
+    if (more) gload((kt + 1) * BKT);
+#pragma unroll
+    for (int s = 0; s < BKT / 16; ++s) {
+      fload(par, s);
+      fmma();
+    }
+    if (more) lstore(par ^ 1);
+    __syncthreads();
+  };
+  gload(0);
+  lstore(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; kt += 2) {
+    step(std::integral_constant<int, 0>{}, kt);
+    if (kt + 1 < nk) step(std::integral_constant<int, 1>{}, kt + 1);
+  }
+  // an inf operand makes the main sum inf; its corrections (inf times a small term of either sign, or 0) are dropped
+#pragma unroll
+  for (int i = 0; i < MB; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] += x3_finite(acc[i][j][e]) ? cor[i][j][e] : 0.f;
+  f32_epilogue<MB, NB>(p, acc, m0, n0, wm, wn, r, kh, p.out);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void softmax_rows_f32_kernel(float* __restrict__ s, long R, int n, int n_valid, float scale) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -707,18 +917,7 @@ __global__ void add_rows_f32_kernel(const float* __restrict__ in, const float* _
 
 }  // namespace f32p
 
-extern "C" int mdt_gemm_f32(const mdt_gemm_f32_args* a, mdt_stream_t stream) {
-  MDT_REQUIRE(a && a->A && a->B && a->out, "gemm_f32: null pointer");
-  MDT_REQUIRE(a->M > 0 && a->N > 0 && a->K >= 4 && a->K % 4 == 0, "gemm_f32: M, N > 0 and K a positive multiple of 4");
-  MDT_REQUIRE(a->lda % 4 == 0 && a->ldb % 4 == 0 && (((uintptr_t)a->A | (uintptr_t)a->B) & 15) == 0,
-              "gemm_f32: operand rows must be 16-byte aligned");
-  MDT_REQUIRE(a->epi >= MDT_F32EPI_NONE && a->epi <= MDT_F32EPI_GATE_RES, "gemm_f32: unknown epilogue");
-  MDT_REQUIRE(a->epi != MDT_F32EPI_GATE_RES || (a->res && a->rows_per_sample > 0), "gemm_f32: GATE_RES needs res and rows_per_sample");
-  const int batch = a->batch > 0 ? a->batch : 1;
-  const int heads = a->heads > 0 ? a->heads : 1;
-  MDT_REQUIRE(batch % heads == 0 && batch <= 65535, "gemm_f32: batch must be a multiple of heads and <= 65535");
-  if (a->b_kmajor) MDT_REQUIRE(a->N % 4 == 0, "gemm_f32: k-major B needs N % 4 == 0");
-  MDT_REQUIRE(((a->a_stride_b | a->a_stride_h | a->b_stride_b | a->b_stride_h) & 3) == 0, "gemm_f32: batch strides must be multiples of 4 elements");
+static f32p::Params f32_params(const mdt_gemm_f32_args* a, int heads) {
   f32p::Params p;
   p.A = a->A; p.lda = a->lda; p.B = a->B; p.ldb = a->ldb;
   p.M = a->M; p.N = a->N; p.K = a->K;
@@ -734,6 +933,39 @@ extern "C" int mdt_gemm_f32(const mdt_gemm_f32_args* a, mdt_stream_t stream) {
              (!a->res || (a->ldres % 4 == 0 && ((uintptr_t)a->res & 15) == 0)) &&
              (!a->gate || (a->gate_ld % 4 == 0 && ((uintptr_t)a->gate & 15) == 0));
   p.dbg = 0;
+  return p;
+}
+
+// The Linear layers of the bf16x3 plan (gemm_bf16x3_kernel): mdt_gemm_f32's contract without the batched / k-major forms
+// -- attention stays exact fp32.
+extern "C" int mdt_gemm_bf16x3(const mdt_gemm_f32_args* a, mdt_stream_t stream) {
+  MDT_REQUIRE(a && a->A && a->B && a->out, "gemm_bf16x3: null pointer");
+  MDT_REQUIRE(a->M > 0 && a->N > 0 && a->K >= 4 && a->K % 4 == 0, "gemm_bf16x3: M, N > 0 and K a positive multiple of 4");
+  MDT_REQUIRE(a->batch <= 1 && a->heads <= 1 && !a->b_kmajor, "gemm_bf16x3: linear layers only (batched / k-major B: mdt_gemm_f32)");
+  MDT_REQUIRE(a->lda % 4 == 0 && a->ldb % 4 == 0 && (((uintptr_t)a->A | (uintptr_t)a->B) & 15) == 0,
+              "gemm_bf16x3: operand rows must be 16-byte aligned");
+  MDT_REQUIRE(a->epi >= MDT_F32EPI_NONE && a->epi <= MDT_F32EPI_GATE_RES, "gemm_bf16x3: unknown epilogue");
+  MDT_REQUIRE(a->epi != MDT_F32EPI_GATE_RES || (a->res && a->rows_per_sample > 0), "gemm_bf16x3: GATE_RES needs res and rows_per_sample");
+  const long tm = cdiv(a->M, 128), tn = cdiv(a->N, 128);
+  MDT_REQUIRE(tm * tn <= 2147483647L, "gemm_bf16x3: too many tiles");
+  const f32p::Params p = f32_params(a, 1);
+  hipLaunchKernelGGL(f32p::gemm_bf16x3_kernel, dim3((unsigned)(tm * tn)), dim3(512), 0, (hipStream_t)stream, p, (int)tm, (int)tn);
+  return mdt_check_launch("gemm_bf16x3");
+}
+
+extern "C" int mdt_gemm_f32(const mdt_gemm_f32_args* a, mdt_stream_t stream) {
+  MDT_REQUIRE(a && a->A && a->B && a->out, "gemm_f32: null pointer");
+  MDT_REQUIRE(a->M > 0 && a->N > 0 && a->K >= 4 && a->K % 4 == 0, "gemm_f32: M, N > 0 and K a positive multiple of 4");
+  MDT_REQUIRE(a->lda % 4 == 0 && a->ldb % 4 == 0 && (((uintptr_t)a->A | (uintptr_t)a->B) & 15) == 0,
+              "gemm_f32: operand rows must be 16-byte aligned");
+  MDT_REQUIRE(a->epi >= MDT_F32EPI_NONE && a->epi <= MDT_F32EPI_GATE_RES, "gemm_f32: unknown epilogue");
+  MDT_REQUIRE(a->epi != MDT_F32EPI_GATE_RES || (a->res && a->rows_per_sample > 0), "gemm_f32: GATE_RES needs res and rows_per_sample");
+  const int batch = a->batch > 0 ? a->batch : 1;
+  const int heads = a->heads > 0 ? a->heads : 1;
+  MDT_REQUIRE(batch % heads == 0 && batch <= 65535, "gemm_f32: batch must be a multiple of heads and <= 65535");
+  if (a->b_kmajor) MDT_REQUIRE(a->N % 4 == 0, "gemm_f32: k-major B needs N % 4 == 0");
+  MDT_REQUIRE(((a->a_stride_b | a->a_stride_h | a->b_stride_b | a->b_stride_h) & 3) == 0, "gemm_f32: batch strides must be multiples of 4 elements");
+  f32p::Params p = f32_params(a, heads);
 #ifdef MDT_EXPERIMENTS
   {
     static int ablate = -1;

@@ -317,9 +317,8 @@ class Engine:
         depend on the padded count -- the exact one is a run-time argument of the four launches that read it
         (PassPlan.set_valid)."""
         global _PLAN_CLOCK
-        if precision not in ('bf16', 'fp32'):
-            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
-        if precision == 'fp32' and (masked or train):
+        check_precision(precision)
+        if reads_f32_arena(precision) and (masked or train):
             raise NotImplementedError('the fp32-faithful path covers inference (the sampler / eval forward: sample.py:56); '
                                       'fp32 TRAINING (train.py --no_amp) is not provided')
         Lv = (L if L is not None else self.sp.T // 2) if masked else None
@@ -335,7 +334,7 @@ class Engine:
             # until it fits (5 % of the device stays free for the caller's own tensors) or nothing is left to drop.
             while len(self._plans) >= 8:
                 _drop_plan(self, next(iter(self._plans)))
-            need = PassPlan.estimate_bytes(self.sp, B, masked, train, Lv) * (2 if precision == 'fp32' else 1)
+            need = PassPlan.estimate_bytes(self.sp, B, masked, train, Lv) * (2 if reads_f32_arena(precision) else 1)
             # (a plan something else still refers to -- a pending backward, a captured sampler graph -- gives no memory back
             # when its cache entry goes: after two evictions in a row that freed nothing the loop stops instead of emptying
             # every engine's cache for no gain)
@@ -366,6 +365,23 @@ class Engine:
 
 
 _PLAN_CLOCK = 0
+
+# Inference arithmetics of Engine.plan: 'bf16' = the training kernels (bf16 shadows of the weights); 'fp32' = exact fp32
+# (csrc/f32path.hip); 'bf16x3' = the fp32 plan with its Linear layers on mdt_gemm_bf16x3 (fp32-level accuracy on the bf16
+# matrix instruction), attention and everything else as in 'fp32'.
+PRECISIONS = ('bf16', 'fp32', 'bf16x3')
+
+
+def check_precision(precision: str) -> str:
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {', '.join(map(repr, PRECISIONS))}, got {precision!r}")
+    return precision
+
+
+def reads_f32_arena(precision: str) -> bool:
+    """A plan of this precision reads the fp32 master arena itself (no bf16 shadow): the fp32-faithful builder, inference
+    only."""
+    return precision != 'bf16'
 
 
 def plan_key(B: int, masked: bool, train: bool, Lv: Optional[int] = None, precision: str = 'bf16') -> tuple:
@@ -461,7 +477,7 @@ class PassPlan:
         self.fwd = Plan()
         self.bwd = Plan()
         self.gen = 0  # forward generation: the saved activations belong to the LAST forward through this plan
-        if precision == 'fp32':
+        if reads_f32_arena(precision):
             self._build_f32()
         else:
             self._build()
@@ -700,7 +716,8 @@ class PassPlan:
         autocast in generate.py): fp32 master weights straight from the parameter arena (no bf16 shadow is read), fp32
         activations, fp32-input MFMA GEMMs (mdt_gemm_f32), attention as q k^T -> row softmax -> p v over the packed qkv
         buffer.  Same graph as _build (DiT.forward, models/maskdit.py:511-557, unmasked), same input / output buffers
-        ('xin', 'coef', 'labels', 'F'), so the sampler and EDMPrecond.forward drive either plan the same way."""
+        ('xin', 'coef', 'labels', 'F'), so the sampler and EDMPrecond.forward drive either plan the same way.  Precision
+        'bf16x3' builds the same graph with every Linear layer on mdt_gemm_bf16x3 (see _g32)."""
         eng, sp, lay = self.eng, self.eng.sp, self.eng.lay
         B, T, D, Dd = self.B, self.T, sp.D, sp.Dd
         NM = sp.n_mod
@@ -759,7 +776,8 @@ class PassPlan:
 
     def _g32(self, A, lda, Bw, ldb, M, N, K, out, ldo, bias=0, epi=F32EPI_NONE, res=None, ldres=0, gate=0, gate_ld=0, rps=1,
              b_kmajor=0, batch=0, heads=0, a_s=(0, 0), b_s=(0, 0), o_s=(0, 0)):
-        """One mdt_gemm_f32 launch; A / out / res are tensors or raw addresses, Bw / bias / gate raw addresses."""
+        """One mdt_gemm_f32 launch -- mdt_gemm_bf16x3 for a Linear layer of a 'bf16x3' plan; A / out / res are tensors or
+        raw addresses, Bw / bias / gate raw addresses."""
         ptr = lambda t: t if isinstance(t, int) else t.data_ptr()  # noqa: E731
         a = GemmF32Args()
         a.A, a.lda, a.B, a.ldb, a.b_kmajor = ptr(A), lda, Bw, ldb, b_kmajor
@@ -772,7 +790,8 @@ class PassPlan:
         a.a_stride_b, a.a_stride_h = a_s
         a.b_stride_b, a.b_stride_h = b_s
         a.o_stride_b, a.o_stride_h = o_s
-        self.fwd.add('mdt_gemm_f32', C.byref(self._k(a)))
+        x3 = self.precision == 'bf16x3' and batch <= 1 and not b_kmajor
+        self.fwd.add('mdt_gemm_bf16x3' if x3 else 'mdt_gemm_f32', C.byref(self._k(a)))
 
     def _block_fwd_f32(self, prefix, tag, i, x_in, mod, moff, W, heads, rows, M):
         """DiTBlock.forward (models/maskdit.py:188-192) in fp32; all blocks of a stack share one buffer set."""
@@ -946,7 +965,7 @@ class PassPlan:
 
     # ---- execution ---------------------------------------------------------------------------
     def run_forward(self) -> int:
-        if self.eng.shadows_dirty and self.precision != 'fp32':  # (an fp32 plan reads the master arena itself)
+        if self.eng.shadows_dirty and not reads_f32_arena(self.precision):  # (an fp32 / bf16x3 plan reads the master arena itself)
             self.eng.refresh_shadows()
         self.gen += 1
         self.fwd.run(torch.cuda.current_stream().cuda_stream)

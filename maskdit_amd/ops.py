@@ -136,23 +136,38 @@ def gemm_f32(A, Bw, out, M, N, K, lda=None, ldb=None, ldo=None, bias=None, epi=F
              rows_per_sample=1, b_kmajor=False, batch=0, heads=0, a_strides=(0, 0), b_strides=(0, 0), o_strides=(0, 0),
              a_off=0, b_off=0, o_off=0):
     """out[z] = A[z][M,K] @ B[z]^T (+ bias) in exact fp32 (mdt_gemm_f32); *_off = element offsets into the tensors."""
-    for t, nm in ((A, 'A'), (Bw, 'B'), (out, 'out')):
-        if t.dtype != torch.float32 or not t.is_cuda:
-            raise ValueError(f'{nm}: expected a CUDA float32 tensor')
-    a = GemmF32Args()
-    a.A, a.lda = A.data_ptr() + 4 * a_off, (A.stride(0) if lda is None else lda)
-    a.B, a.ldb, a.b_kmajor = Bw.data_ptr() + 4 * b_off, (Bw.stride(0) if ldb is None else ldb), int(b_kmajor)
-    a.M, a.N, a.K = M, N, K
-    a.bias, a.epi = p(bias), epi
-    a.out, a.ldo = out.data_ptr() + 4 * o_off, (out.stride(0) if ldo is None else ldo)
-    a.res, a.ldres = p(res), (res.stride(0) if res is not None else 0)
-    a.gate, a.gate_ld, a.rows_per_sample = p(gate), gate_ld, rows_per_sample
+    a = _gemm_f32_args(A, Bw, out, M, N, K, lda, ldb, ldo, bias, epi, res, gate, gate_ld, rows_per_sample, a_off, b_off, o_off)
+    a.b_kmajor = int(b_kmajor)
     a.batch, a.heads = batch, heads
     a.a_stride_b, a.a_stride_h = a_strides
     a.b_stride_b, a.b_stride_h = b_strides
     a.o_stride_b, a.o_stride_h = o_strides
     call('mdt_gemm_f32', C.byref(a), stream_ptr())
     return out
+
+
+def gemm_bf16x3(A, Bw, out, M, N, K, lda=None, ldb=None, ldo=None, bias=None, epi=F32EPI_NONE, res=None, gate=None, gate_ld=0,
+                rows_per_sample=1, a_off=0, b_off=0, o_off=0):
+    """out = A[M,K] @ B[N,K]^T (+ bias) at fp32-level accuracy on the bf16 matrix instruction (mdt_gemm_bf16x3: three-term
+    bf16 split of both operands, six cross products); the Linear-layer form of gemm_f32, same epilogues."""
+    a = _gemm_f32_args(A, Bw, out, M, N, K, lda, ldb, ldo, bias, epi, res, gate, gate_ld, rows_per_sample, a_off, b_off, o_off)
+    call('mdt_gemm_bf16x3', C.byref(a), stream_ptr())
+    return out
+
+
+def _gemm_f32_args(A, Bw, out, M, N, K, lda, ldb, ldo, bias, epi, res, gate, gate_ld, rows_per_sample, a_off, b_off, o_off):
+    for t, nm in ((A, 'A'), (Bw, 'B'), (out, 'out')):
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError(f'{nm}: expected a CUDA float32 tensor')
+    a = GemmF32Args()
+    a.A, a.lda = A.data_ptr() + 4 * a_off, (A.stride(0) if lda is None else lda)
+    a.B, a.ldb = Bw.data_ptr() + 4 * b_off, (Bw.stride(0) if ldb is None else ldb)
+    a.M, a.N, a.K = M, N, K
+    a.bias, a.epi = p(bias), epi
+    a.out, a.ldo = out.data_ptr() + 4 * o_off, (out.stride(0) if ldo is None else ldo)
+    a.res, a.ldres = p(res), (res.stride(0) if res is not None else 0)
+    a.gate, a.gate_ld, a.rows_per_sample = p(gate), gate_ld, rows_per_sample
+    return a
 
 
 def attention_f32(qkv, B, L, H, hd, three_launch=False):

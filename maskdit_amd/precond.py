@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import call
-from .engine import MODEL_CONFIGS, Engine, Spec, make_spec
+from .engine import MODEL_CONFIGS, Engine, Spec, check_precision, make_spec
 
 
 # ------------------------------------------------------------------------------------------
@@ -217,7 +217,8 @@ class EDMPrecond(nn.Module):
         self._grad_items = None  # (gradient arena, [(parameter, its arena view)]) -- see _prepare_grad_arena
         # arithmetic of INFERENCE evaluations (no-grad forward, forward_with_cfg, edm_sampler): 'bf16' = the training
         # kernels (bf16 MFMA operands, fp32 residual stream -- the reference under autocast); 'fp32' = exact fp32 throughout
-        # (csrc/f32path.hip), what the reference's own sampler runs (sample.py:56, no autocast in generate.py).
+        # (csrc/f32path.hip), what the reference's own sampler runs (sample.py:56, no autocast in generate.py); 'bf16x3' = that
+        # plan with its Linear layers on mdt_gemm_bf16x3.
         self.eval_precision = 'bf16'
 
     # ---- engine binding ------------------------------------------------------------------
@@ -295,10 +296,9 @@ class EDMPrecond(nn.Module):
         return torch.as_tensor(sigma)
 
     def set_eval_precision(self, precision: str):
-        """'bf16' (default) or 'fp32' (the reference sampler's own arithmetic; ~1/8 of the bf16 throughput)."""
-        if precision not in ('bf16', 'fp32'):
-            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
-        self.eval_precision = precision
+        """'bf16' (default), 'fp32' (the reference sampler's own arithmetic; ~1/8 of the bf16 throughput) or 'bf16x3' (the
+        fp32 plan with its Linear layers on the bf16 matrix instruction through a three-term split of every operand)."""
+        self.eval_precision = check_precision(precision)
         return self
 
     # ---- gradient plumbing ---------------------------------------------------------------

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import call
-from .engine import plan_key
+from .engine import check_precision, plan_key, reads_f32_arena
 from .loss import unwrap_model
 from .precond import EDMPrecond
 
@@ -88,7 +88,7 @@ class _GraphedHeun:
     def capture(self, cfg_scale: float):
         L = _lib.lib()
         self.destroy()
-        if self.eng.shadows_dirty and self.precision != 'fp32':
+        if self.eng.shadows_dirty and not reads_f32_arena(self.precision):
             self.eng.refresh_shadows()
         torch.cuda.synchronize()
         graphs = []
@@ -176,7 +176,9 @@ def edm_sampler(net, latents, class_labels=None, cfg_scale=None, feat=None, rand
     network evaluations -- 'bf16' (bf16 MFMA operands, fp32 residual stream: the training kernels; 18-19 samples/s for XL/2,
     drift 7e-4 of the latent range against the reference's fp32 network after 50 steps) or 'fp32' (exact fp32 weights,
     activations and matrix instructions: what sample.py:56 itself runs, agreeing with the reference fixture to fp32
-    rounding); None = the network's `eval_precision` (default 'bf16')."""
+    rounding) or 'bf16x3' (the fp32 plan with its Linear layers on the bf16 matrix instruction, each fp32 operand split
+    into three bf16 terms: the same fixture bound as 'fp32', faster); None = the network's `eval_precision` (default
+    'bf16')."""
     raw = unwrap_model(net)
     if not isinstance(raw, EDMPrecond):
         raise TypeError(f'maskdit_amd.edm_sampler expects a maskdit_amd EDMPrecond, got {type(raw).__name__}')
@@ -193,8 +195,7 @@ def edm_sampler(net, latents, class_labels=None, cfg_scale=None, feat=None, rand
     labels = raw._labels(class_labels, B, latents.device)
     x_next = latents.to(torch.float64) * t_steps[0]  # sample.py:46
     precision = raw.eval_precision if precision is None else precision
-    if precision not in ('bf16', 'fp32'):
-        raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+    check_precision(precision)
     if S_churn != 0:
         # stochastic churn (sample.py:51-53; no shipped config uses it): every network evaluation is the HIP forward
         # plan, the fp64 state algebra of the step -- which now carries a per-step noise level t_hat != t_i -- is torch
@@ -209,8 +210,8 @@ def edm_sampler(net, latents, class_labels=None, cfg_scale=None, feat=None, rand
     if num_steps + 1 > g.t_steps.numel():
         raise ValueError('num_steps exceeds the captured schedule capacity (1024)')
     s = float(cfg_scale) if use_cfg else 0.0
-    # (an fp32 plan reads the fp32 master arena: stale bf16 shadows do not concern its captured graphs)
-    stale = raw.engine().shadows_dirty and precision != 'fp32'
+    # (an fp32 / bf16x3 plan reads the fp32 master arena: stale bf16 shadows do not concern its captured graphs)
+    stale = raw.engine().shadows_dirty and not reads_f32_arena(precision)
     if use_graph and (g.graph_full is None or g.captured_cfg != s or stale):
         g.capture(s)
     if not use_graph and stale:

@@ -71,7 +71,9 @@ WATCH = {
     'gemm.hip': [(r'gemm_(nt|tn)_kernel', 'generic')],
     # round 6: the fp32 path -- gemm_f32_dma_kernel moves its tiles by LDS-DMA (drained by the vmcnt(0) of __syncthreads) and
     # reads its fragments with inline-asm ds_read + hand-placed lgkmcnt waits
-    'f32path.hip': [(r'gemm_f32_dma_kernel', 'generic'), (r'gemm_f32_kernel', 'generic'), (r'attn_f32_kernel', 'generic')],
+    # gemm_bf16x3_kernel: register-staged like gemm_f32_kernel (the operand split sits between the global loads and ds_write)
+    'f32path.hip': [(r'gemm_f32_dma_kernel', 'generic'), (r'gemm_f32_kernel', 'generic'), (r'attn_f32_kernel', 'generic'),
+                    (r'gemm_bf16x3_kernel', 'generic')],
 }
 
 
