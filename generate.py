@@ -4,9 +4,11 @@ the MI355X engine: per-seed StackedRandomGenerator latents / labels (utils.py:11
 hipGraph-captured EDM Heun sampler with classifier-free guidance, latents written as .npy.
 
     python generate.py --config configs/xl2-256-synthetic.yaml --seeds 0-63 --num_steps 50 --cfg_scale 1.5 \
-        [--ckpt_path 2000000.pt] [--outdir samples] [--precision fp32]
+        [--ckpt_path 2000000.pt] [--outdir samples] [--precision fp32] [--S_churn N]
+        [--solver euler|heun] [--discretization vp|ve|iddpm|edm] [--schedule vp|ve|linear] [--scaling vp|none]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 generate.py ...   # seeds sharded by rank
 
+Any of --solver/--discretization/--schedule/--scaling switches to the generalized ablation_sampler (sample.py:240-245).
 Seeds are split over the ranks exactly as sample.py:233-235 does (no exchange step: replicas only).
 `--pretrained_path autoencoder_kl.pth` adds the reference's decode step (sample.py:248,273-296): the latents go through
 maskdit_amd.autoencoder (HIP) and are written as uint8 images (`.png` when PIL is importable, else `.npy`); without it the
@@ -21,6 +23,7 @@ import numpy as np
 import torch
 
 import maskdit_amd as M
+from maskdit_amd.ablation import add_sampler_args, select_sampler
 from maskdit_amd.schedule import load_config
 
 
@@ -60,7 +63,10 @@ def main(argv=None):
                          "the reference's own sampler runs (sample.py:56; ~1/9 of the bf16 throughput); 'bf16x3' = the same fp32 "
                          "network with its Linear layers on the bf16 matrix instruction (every fp32 operand split exactly into three "
                          "bf16 terms, six cross products summed in fp32: fp32-level accuracy); 'bf16' = the training kernels")
+    add_sampler_args(ap)  # sample.py:357-363: any of --solver/--discretization/--schedule/--scaling -> ablation_sampler
     args = ap.parse_args(argv)
+    sampler_fn, sampler_kwargs = select_sampler(args.num_steps, args.S_churn, args.solver, args.discretization, args.schedule,
+                                                args.scaling)
     cfg = load_config(args.config)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -88,8 +94,8 @@ def main(argv=None):
         if args.class_idx is not None:
             labels[:, :] = 0
             labels[:, args.class_idx] = 1
-        z = M.edm_sampler(net, latents, labels, cfg_scale=args.cfg_scale, randn_like=rnd.randn_like, num_steps=args.num_steps,
-                          precision=args.precision)
+        z = sampler_fn(net, latents, labels, cfg_scale=args.cfg_scale, randn_like=rnd.randn_like, precision=args.precision,
+                       **sampler_kwargs)
         images = None
         if vae is not None:  # sample.py:282-286: decode, [-1, 1] -> uint8 HWC
             images = vae.decode(z.float()).add_(1).mul_(127.5).clamp_(0, 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()

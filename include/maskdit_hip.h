@@ -261,6 +261,41 @@ int mdt_sampler_advance(int32_t* step_idx, mdt_stream_t stream);
 /* classifier-free guidance combine on F = [cond; uncond] (models/maskdit.py:580-583), n = B*chw */
 int mdt_cfg_combine(const float* F, float cfg_scale, float* out, long n, mdt_stream_t stream);
 
+/* ablation_sampler (sample.py:73-188): the generalized EDM step.  `table` is a device fp64 [steps, MDT_ABL_NCOL] table
+ * whose row *step_idx holds every per-step scalar of the step (maskdit_amd/ablation.py builds it); the entries read that
+ * row, so one captured hipGraph serves every step of every discretization / schedule / scaling.  State fp64. */
+#define MDT_ABL_A 0      /* s(t_hat) / s(t_cur)                                    x_hat = A x_cur + C noise     */
+#define MDT_ABL_C 1      /* sqrt(max(sigma(t_hat)^2 - sigma(t_cur)^2, 0)) s(t_hat) S_noise                      */
+#define MDT_ABL_SIG 2    /* sigma(t_hat): the network's noise level                                             */
+#define MDT_ABL_S 3      /* s(t_hat): the network input is float(x_hat) / float(s)                              */
+#define MDT_ABL_P 4      /* sigma'/sigma + s'/s at t_hat                           d = P x - Q D                 */
+#define MDT_ABL_Q 5      /* sigma' s / sigma at t_hat                                                           */
+#define MDT_ABL_SIG2 6   /* the same four at t_prime = t_hat + alpha h (second evaluation)                      */
+#define MDT_ABL_S2 7
+#define MDT_ABL_P2 8
+#define MDT_ABL_Q2 9
+#define MDT_ABL_H 10     /* h = t_next - t_hat                                                                  */
+#define MDT_ABL_AH 11    /* alpha h                                                                             */
+#define MDT_ABL_W1 12    /* 1 - 1 / (2 alpha)                                                                   */
+#define MDT_ABL_W2 13    /* 1 / (2 alpha)                                                                       */
+#define MDT_ABL_SECOND 14 /* 1: the step takes the second evaluation (heun and not the last step), else 0       */
+#define MDT_ABL_NCOL 16
+/* which = 0: x_hat = A x + C noise (written), network input from x_hat at SIG / S;  which = 1: network input from x
+ * (= x_prime) at SIG2 / S2, x_hat and noise untouched.  xin [dup copies] = c_in(sigma) * (float(x) / float(s));
+ * sigma_out [B*dup] = float(sigma).  dup = 2 for classifier-free guidance. */
+int mdt_ablation_prep(const double* x, const double* noise, const double* table, const int32_t* step_idx, int which,
+                      double* x_hat, float* xin, float* sigma_out, int B, int chw, int dup, float sigma_data,
+                      mdt_stream_t stream);
+/* D = c_skip x_in + c_out F (fused CFG combine when use_cfg), d_cur = P x_hat - Q D; then x = x_hat + AH d_cur
+ * (x_prime) when SECOND, else x = x_hat + H d_cur (x_next). */
+int mdt_ablation_slope1(const double* x_hat, const float* F, const double* table, const int32_t* step_idx,
+                        float cfg_scale, int use_cfg, double* d_cur, double* x, int B, int chw, float sigma_data,
+                        mdt_stream_t stream);
+/* d' = P2 x - Q2 D' at x = x_prime, then x = x_hat + H (W1 d_cur + W2 d') (x_next, in place). */
+int mdt_ablation_slope2(const double* x_hat, double* x, const float* F, const double* d_cur, const double* table,
+                        const int32_t* step_idx, float cfg_scale, int use_cfg, int B, int chw, float sigma_data,
+                        mdt_stream_t stream);
+
 /* ---------------------------------------------------------------- fp32-faithful inference path ---- */
 
 /* The reference's sampler evaluates its network in fp32 (sample.py:56 `net(x_hat.float(), ...)`; generate.py has no

@@ -85,6 +85,9 @@ _PROTOS = {
     'mdt_sampler_heun': [vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, f32],
     'mdt_sampler_advance': [vp],
     'mdt_cfg_combine': [vp, f32, vp, i64],
+    'mdt_ablation_prep': [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, f32],
+    'mdt_ablation_slope1': [vp, vp, vp, vp, f32, i32, vp, vp, i32, i32, f32],
+    'mdt_ablation_slope2': [vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, f32],
     'mdt_gn_stats': [vp, vp, i32, i32, i32, i32],
     'mdt_gn_im2col': [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32],
     'mdt_conv3x3_nhwc': [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32],

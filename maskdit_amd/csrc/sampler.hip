@@ -124,3 +124,113 @@ extern "C" int mdt_cfg_combine(const float* F, float cfg_scale, float* out, long
   hipLaunchKernelGGL(cfg_combine_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, F, cfg_scale, out, n);
   return mdt_check_launch("cfg_combine");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// ablation_sampler (sample.py:73-188): the generalized step reads every per-step scalar from row *step_idx of an fp64
+// table (MDT_ABL_* columns, include/maskdit_hip.h), so one captured graph serves every step of every discretization,
+// schedule and scaling.  FP contraction is off: each fp64 / fp32 operation rounds once, as the reference's torch ops do.
+
+__device__ __forceinline__ float ablation_denoise(float xi, const float* F, long idx, long n, float sigma, float sd,
+                                                  float cfg_scale, int use_cfg) {
+#pragma clang fp contract(off)
+  float f = F[idx];
+  if (use_cfg) {
+    float fu = F[n + idx];
+    f = fu + cfg_scale * (f - fu);
+  }
+  float cs, co, ci;
+  precond_f(sigma, sd, cs, co, ci);
+  return cs * xi + co * f;  // D = c_skip * x_in + c_out * F, x_in = float(x) / s (models/maskdit.py:771)
+}
+
+__global__ void ablation_prep_kernel(const double* __restrict__ x, const double* __restrict__ noise,
+                                     const double* __restrict__ table, const int32_t* __restrict__ step_idx, int which,
+                                     double* __restrict__ x_hat, float* __restrict__ xin, float* __restrict__ sigma_out,
+                                     int B, int chw, int dup, float sd) {
+#pragma clang fp contract(off)
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = (long)B * chw;
+  const double* row = table + (long)*step_idx * MDT_ABL_NCOL;
+  const float sigma = (float)row[which ? MDT_ABL_SIG2 : MDT_ABL_SIG];
+  const float s = (float)row[which ? MDT_ABL_S2 : MDT_ABL_S];
+  if (idx < (long)B * dup) sigma_out[idx] = sigma;
+  if (idx >= n) return;
+  double v = x[idx];
+  if (!which) {
+    v = row[MDT_ABL_A] * v + row[MDT_ABL_C] * noise[idx];  // sample.py:167
+    x_hat[idx] = v;
+  }
+  float cs, co, ci;
+  precond_f(sigma, sd, cs, co, ci);
+  const float xi = ci * ((float)v / s);  // sample.py:172 x_hat.float() / s(t_hat), then c_in (models/maskdit.py:769)
+  xin[idx] = xi;
+  if (dup > 1) xin[n + idx] = xi;
+}
+
+__global__ void ablation_slope1_kernel(const double* __restrict__ x_hat, const float* __restrict__ F,
+                                       const double* __restrict__ table, const int32_t* __restrict__ step_idx,
+                                       float cfg_scale, int use_cfg, double* __restrict__ d_cur, double* __restrict__ x,
+                                       long n, float sd) {
+#pragma clang fp contract(off)
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  const double* row = table + (long)*step_idx * MDT_ABL_NCOL;
+  const double xh = x_hat[idx];
+  const float xi = (float)xh / (float)row[MDT_ABL_S];
+  const double den = (double)ablation_denoise(xi, F, idx, n, (float)row[MDT_ABL_SIG], sd, cfg_scale, use_cfg);
+  const double d = row[MDT_ABL_P] * xh - row[MDT_ABL_Q] * den;  // sample.py:173-174
+  d_cur[idx] = d;
+  // sample.py:175 x_prime for the second evaluation, or sample.py:180 x_next
+  x[idx] = xh + (row[MDT_ABL_SECOND] != 0.0 ? row[MDT_ABL_AH] : row[MDT_ABL_H]) * d;
+}
+
+__global__ void ablation_slope2_kernel(const double* __restrict__ x_hat, double* __restrict__ x,
+                                       const float* __restrict__ F, const double* __restrict__ d_cur,
+                                       const double* __restrict__ table, const int32_t* __restrict__ step_idx,
+                                       float cfg_scale, int use_cfg, long n, float sd) {
+#pragma clang fp contract(off)
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  const double* row = table + (long)*step_idx * MDT_ABL_NCOL;
+  const double xp = x[idx];
+  const float xi = (float)xp / (float)row[MDT_ABL_S2];
+  const double den = (double)ablation_denoise(xi, F, idx, n, (float)row[MDT_ABL_SIG2], sd, cfg_scale, use_cfg);
+  const double dp = row[MDT_ABL_P2] * xp - row[MDT_ABL_Q2] * den;  // sample.py:184-185
+  x[idx] = x_hat[idx] + row[MDT_ABL_H] * (row[MDT_ABL_W1] * d_cur[idx] + row[MDT_ABL_W2] * dp);  // sample.py:186
+}
+
+extern "C" int mdt_ablation_prep(const double* x, const double* noise, const double* table, const int32_t* step_idx,
+                                 int which, double* x_hat, float* xin, float* sigma_out, int B, int chw, int dup,
+                                 float sigma_data, mdt_stream_t stream) {
+  MDT_REQUIRE(x && table && step_idx && xin && sigma_out, "ablation_prep: null pointer");
+  MDT_REQUIRE(which == 0 || which == 1, "ablation_prep: which must be 0 or 1");
+  MDT_REQUIRE(which == 1 || (noise && x_hat), "ablation_prep: which = 0 needs noise and x_hat");
+  MDT_REQUIRE(dup == 1 || dup == 2, "ablation_prep: dup must be 1 or 2");
+  MDT_REQUIRE(B > 0 && chw >= dup, "ablation_prep: bad shape");
+  long n = (long)B * chw;
+  hipLaunchKernelGGL(ablation_prep_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x, noise, table,
+                     step_idx, which, x_hat, xin, sigma_out, B, chw, dup, sigma_data);
+  return mdt_check_launch("ablation_prep");
+}
+
+extern "C" int mdt_ablation_slope1(const double* x_hat, const float* F, const double* table, const int32_t* step_idx,
+                                   float cfg_scale, int use_cfg, double* d_cur, double* x, int B, int chw,
+                                   float sigma_data, mdt_stream_t stream) {
+  MDT_REQUIRE(x_hat && F && table && step_idx && d_cur && x, "ablation_slope1: null pointer");
+  MDT_REQUIRE(B > 0 && chw > 0, "ablation_slope1: bad shape");
+  long n = (long)B * chw;
+  hipLaunchKernelGGL(ablation_slope1_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x_hat, F, table,
+                     step_idx, cfg_scale, use_cfg, d_cur, x, n, sigma_data);
+  return mdt_check_launch("ablation_slope1");
+}
+
+extern "C" int mdt_ablation_slope2(const double* x_hat, double* x, const float* F, const double* d_cur,
+                                   const double* table, const int32_t* step_idx, float cfg_scale, int use_cfg, int B,
+                                   int chw, float sigma_data, mdt_stream_t stream) {
+  MDT_REQUIRE(x_hat && x && F && d_cur && table && step_idx, "ablation_slope2: null pointer");
+  MDT_REQUIRE(B > 0 && chw > 0, "ablation_slope2: bad shape");
+  long n = (long)B * chw;
+  hipLaunchKernelGGL(ablation_slope2_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x_hat, x, F, d_cur,
+                     table, step_idx, cfg_scale, use_cfg, n, sigma_data);
+  return mdt_check_launch("ablation_slope2");
+}

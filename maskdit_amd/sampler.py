@@ -121,12 +121,14 @@ class _GraphedHeun:
 
 
 _CACHE: Dict[Tuple[int, int, bool, str], _GraphedHeun] = {}
+_CACHES = [_CACHE]  # every sampler graph cache (maskdit_amd.ablation adds its own)
 
 
 def release_graphs():
     """Destroy every cached sampler graph (and with it the references to the inference plans they replay)."""
-    while _CACHE:
-        _CACHE.popitem()[1].destroy()
+    for cache in _CACHES:
+        while cache:
+            cache.popitem()[1].destroy()
 
 
 def _graphed(net: EDMPrecond, B: int, use_cfg: bool, precision: str = 'bf16') -> _GraphedHeun:

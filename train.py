@@ -27,6 +27,7 @@ import torch
 import torch.distributed as dist
 
 import maskdit_amd as M
+from maskdit_amd.ablation import add_sampler_args, select_sampler
 from maskdit_amd.schedule import get_mask_ratio_fn, get_one_hot, load_config, lr_rampup_factor
 
 
@@ -163,6 +164,9 @@ def evaluate_in_loop(args, cfg, ema, dev, rank, world, exp_dir, step):
     latent statistics."""
     import numpy as np
     outdir = os.path.join(exp_dir, 'fid', f'edm-steps{args.num_steps}-ckpt{step}_cfg{args.cfg_scale}')
+    # sample.py:240-245: any of --solver/--discretization/--schedule/--scaling -> ablation_sampler
+    sampler_fn, sampler_kwargs = select_sampler(args.num_steps, args.S_churn, args.solver, args.discretization, args.schedule,
+                                                args.scaling)
     os.makedirs(outdir, exist_ok=True)
     was_training = ema.training
     ema.eval()
@@ -173,7 +177,7 @@ def evaluate_in_loop(args, cfg, ema, dev, rank, world, exp_dir, step):
         rnd = M.StackedRandomGenerator(dev, seeds)
         lat = rnd.randn([len(seeds), ema.img_channels, ema.img_resolution, ema.img_resolution], device=dev)
         lab = torch.eye(ema.num_classes, device=dev)[rnd.randint(ema.num_classes, size=[len(seeds)], device=dev)]
-        z = M.edm_sampler(ema, lat, lab, cfg_scale=args.cfg_scale, randn_like=rnd.randn_like, num_steps=args.num_steps)
+        z = sampler_fn(ema, lat, lab, cfg_scale=args.cfg_scale, randn_like=rnd.randn_like, **sampler_kwargs)
         stats += torch.stack([z.sum(), (z * z).sum()])
         for sd, zi in zip(seeds, z.cpu().numpy()):
             np.save(os.path.join(outdir, f'{sd:06d}.npy'), zi)
@@ -219,6 +223,7 @@ def parse(argv=None):
     ap.add_argument('--max_batch_size', type=int, default=64)
     ap.add_argument('--num_steps', type=int, default=40)
     ap.add_argument('--cfg_scale', type=float, default=None)
+    add_sampler_args(ap)  # train.py:322-326
     ap.add_argument('--ref_path', default=None)
     # train.py:305 of the reference: --no_amp = fp32 / TF32 training.  This engine's TRAINING kernels compute in bf16 with an fp32
     # residual stream / fp32 master weights (the reference under autocast); an fp32 backward does not exist.  The flag is
