@@ -14,7 +14,8 @@ ToTensor + Normalize(0.5, 0.5) there.  Output under <outdir>/<data_name>_<resolu
         maskdit_amd.data.WdsTarLatents / train_wds.py read them)
 --xflip stores the mirrored images' moments after the N originals (indices N .. 2N-1), as the reference does.
 --rank / --world (wds only): this process encodes the contiguous slice rank of world (and its mirrored copies) into
-shards of its own, so several GPUs split one dataset.  --ckpt none: seeded synthetic weights (--seed)."""
+shards of its own, so several GPUs split one dataset.  --ckpt none: seeded synthetic weights (--seed).
+--vae_precision bf16x3: the encoder at the reference's fp32 accuracy (default bf16: bf16 operands)."""
 import argparse
 import concurrent.futures as cf
 import os
@@ -71,7 +72,7 @@ class LmdbSink:
         pass
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     ap.add_argument('--data_name', default='imagenet', type=str)
     ap.add_argument('--data_dir', default='../datasets', type=str)
@@ -88,6 +89,13 @@ def main(argv=None):
     ap.add_argument('--world', default=1, type=int)
     ap.add_argument('--workers', default=16, type=int, help='host decode threads (at most 16)')
     ap.add_argument('--device', default='cuda', type=str)
+    ap.add_argument('--vae_precision', default='bf16', choices=list(AE.PRECISIONS),
+                    help="encoder arithmetic: 'bf16x3' = the reference's fp32 accuracy, 'bf16' = bf16 operands (default)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.format == 'lmdb' and args.world != 1:
         ap.error('--rank / --world split the dataset into WebDataset shards: use --format wds')
@@ -100,11 +108,11 @@ def main(argv=None):
     print(f'data size: {N} images in {len(classes)} classes; rank {args.rank}/{args.world} encodes [{lo}, {hi})')
 
     if args.ckpt.lower() == 'none':
-        vae = AE.get_model(None, encoder=True)
+        vae = AE.get_model(None, encoder=True, precision=args.vae_precision)
         vae.load_state_dict(AE.synthetic_state_dict(args.seed))
         print(f'synthetic VAE weights (seed {args.seed})')
     else:
-        vae = AE.get_model(args.ckpt, encoder=True)
+        vae = AE.get_model(args.ckpt, encoder=True, precision=args.vae_precision)
         print(f'load vae weights from {args.ckpt}')
     dev = torch.device(args.device)
     vae = vae.to(dev)

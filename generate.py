@@ -4,14 +4,14 @@ the MI355X engine: per-seed StackedRandomGenerator latents / labels (utils.py:11
 hipGraph-captured EDM Heun sampler with classifier-free guidance, latents written as .npy.
 
     python generate.py --config configs/xl2-256-synthetic.yaml --seeds 0-63 --num_steps 50 --cfg_scale 1.5 \
-        [--ckpt_path 2000000.pt] [--outdir samples] [--precision fp32] [--S_churn N]
+        [--ckpt_path 2000000.pt] [--outdir samples] [--precision fp32] [--vae_precision bf16x3] [--S_churn N]
         [--solver euler|heun] [--discretization vp|ve|iddpm|edm] [--schedule vp|ve|linear] [--scaling vp|none]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 generate.py ...   # seeds sharded by rank
 
 Any of --solver/--discretization/--schedule/--scaling switches to the generalized ablation_sampler (sample.py:240-245).
 Seeds are split over the ranks exactly as sample.py:233-235 does (no exchange step: replicas only).
 `--pretrained_path autoencoder_kl.pth` adds the reference's decode step (sample.py:248,273-296): the latents go through
-maskdit_amd.autoencoder (HIP) and are written as uint8 images (`.png` when PIL is importable, else `.npy`); without it the
+maskdit_amd.autoencoder (HIP; `--vae_precision bf16x3` = at the reference's fp32 accuracy) and are written as uint8 images (`.png` when PIL is importable, else `.npy`); without it the
 fp64 latents `z` are the product (the published VAE weights are not available offline)."""
 from __future__ import annotations
 
@@ -46,7 +46,7 @@ def load_weights(net, path, key='ema'):
     net.load_state_dict({k.replace('_orig_mod.', ''): v for k, v in sd.items()})
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', required=True)
     ap.add_argument('--ckpt_path', default=None)
@@ -63,8 +63,16 @@ def main(argv=None):
                          "the reference's own sampler runs (sample.py:56; ~1/9 of the bf16 throughput); 'bf16x3' = the same fp32 "
                          "network with its Linear layers on the bf16 matrix instruction (every fp32 operand split exactly into three "
                          "bf16 terms, six cross products summed in fp32: fp32-level accuracy); 'bf16' = the training kernels")
+    ap.add_argument('--vae_precision', choices=['bf16', 'bf16x3'], default='bf16',
+                    help="arithmetic of the autoencoder behind --pretrained_path (--precision is the network only): 'bf16x3' = the "
+                         "reference's fp32 accuracy (fp32 operands split into three bf16 terms; autoencoder.py runs in fp32), "
+                         "'bf16' = bf16 operands, fp32 accumulation (about 2 grey levels from the fp32 image)")
     add_sampler_args(ap)  # sample.py:357-363: any of --solver/--discretization/--schedule/--scaling -> ablation_sampler
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     sampler_fn, sampler_kwargs = select_sampler(args.num_steps, args.S_churn, args.solver, args.discretization, args.schedule,
                                                 args.scaling)
     cfg = load_config(args.config)
@@ -82,7 +90,7 @@ def main(argv=None):
     vae = None
     if args.pretrained_path:
         from maskdit_amd import autoencoder
-        vae = autoencoder.get_model(args.pretrained_path).to(dev)
+        vae = autoencoder.get_model(args.pretrained_path, precision=args.vae_precision).to(dev)
     os.makedirs(args.outdir, exist_ok=True)
     t0, n = time.time(), 0
     for seeds in M.seed_batches(args.seeds, args.max_batch_size, rank, world):

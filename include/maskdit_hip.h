@@ -407,6 +407,35 @@ int mdt_vae_enc_prologue(const void* img, int u8, int flip, mdt_bf16* col, int B
 int mdt_vae_enc_epilogue(const float* in, int ld, const float* qw, const float* qb, float* moments, int B, int HW,
                          mdt_stream_t stream);
 
+/* ---------------------------------------------------------------- VAE, fp32-accurate ('bf16x3') ------ */
+
+/* The reference runs its autoencoder in fp32 (autoencoder.py; no autocast in generate.py / extract_latent.py).  The
+ * entries below, with mdt_gemm_bf16x3 (1x1 convolutions, conv_in), mdt_gemm_f32 + mdt_softmax_rows_f32 (attention) and the
+ * fp32 glue above (mdt_add_f32, mdt_vae_prologue / _epilogue / _enc_epilogue), are that arithmetic:
+ * fp32 operands split exactly into three bf16 terms, six cross products on the bf16 matrix instruction, no atomics. */
+/* out[(b, y, x), n] = bias[n] (+ res[(b, y, x), n]) + sum_{ky, kx, c} act[b, sy, sx, c] * W[n, (ky * 3 + kx) * C + c], an
+ * IMPLICIT GEMM in the arithmetic of mdt_gemm_bf16x3 (the kernel gathers the nine taps).  Source pixel (sy, sx):
+ *   up = 0, down = 0: (y + ky - 1, x + kx - 1), zero outside [0, Hi): nn.Conv2d(C, Cout, 3, padding = 1); output side Hi
+ *   up = 1:           ((y + ky - 1) >> 1, (x + kx - 1) >> 1), zero outside the 2 Hi image: Upsample (autoencoder.py:35-52)
+ *   down = 1:         (2 y + ky, 2 x + kx), row / column Hi reading zero: Downsample (:56-75); output side Hi / 2, Hi even
+ * act: fp32 NHWC [B, Hi, Hi, C], C % 32 == 0, 16-byte aligned, and THE 128 BYTES IN FRONT OF `act` MUST BE ZERO (the padding
+ * taps read them).  W: fp32 [Cout, 9 C] (no padding of Cout), bias fp32 [Cout] or NULL, res fp32 [M, ldo] or NULL, out fp32
+ * [M, ldo], M = B * Ho * Ho < 2^31, any Hi and any Cout.  Deterministic: repeated calls give identical bits. */
+int mdt_conv3x3_bf16x3_nhwc(const float* act, int B, int Hi, int C, int up, int down, const float* W, const float* bias,
+                            const float* res, float* out, long ldo, int Cout, mdt_stream_t stream);
+/* mdt_gn_stats in a fixed summation order (no atomics: identical bits on every run): per-workgroup partial sums go to `ws`
+ * (at least mdt_gn_stats_ordered_ws_floats(B, groups) floats) and are folded per (sample, group) in index order, in fp64.
+ * Same shape rules as mdt_gn_stats; B <= 65535. */
+long mdt_gn_stats_ordered_ws_floats(int B, int groups);
+int mdt_gn_stats_ordered(const float* x, float* sums, float* ws, int B, int HW, int C, int groups, mdt_stream_t stream);
+/* mdt_gn_im2col with an fp32 result and exact-form GroupNorm / swish (IEEE division, sqrt, expf): ksize 1 writes the
+ * operand of mdt_conv3x3_bf16x3_nhwc / of the 1x1 convolutions, ksize 3 a materialised im2col matrix (conv_in: C = 4,
+ * K = 36).  C % 4 == 0, Kp % 4 == 0, Kp >= k*k*C. */
+int mdt_gn_im2col_f32(const float* x, const float* sums, const float* gamma, const float* beta, float* col, int B, int H,
+                      int W, int C, int groups, int ksize, int upsample, int swish, int Kp, mdt_stream_t stream);
+/* mdt_vae_enc_prologue with an fp32 result (the same values, not rounded to bf16); Kp % 4 == 0 (K = 27 -> 28). */
+int mdt_vae_enc_prologue_f32(const void* img, int u8, int flip, float* col, int B, int R, int Kp, mdt_stream_t stream);
+
 /* hipGraph helpers (stream capture of a sequence of the calls above). */
 int mdt_graph_begin(mdt_stream_t stream);
 int mdt_graph_end(mdt_stream_t stream, void** graph_exec_out);

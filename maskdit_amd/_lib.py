@@ -97,6 +97,10 @@ _PROTOS = {
     'mdt_conv3x3_down_nhwc': [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32],
     'mdt_vae_enc_prologue': [vp, i32, i32, vp, i32, i32, i32],
     'mdt_vae_enc_epilogue': [vp, i32, vp, vp, vp, i32, i32],
+    'mdt_conv3x3_bf16x3_nhwc': [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, i32],
+    'mdt_gn_stats_ordered': [vp, vp, vp, i32, i32, i32, i32],
+    'mdt_gn_im2col_f32': [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32],
+    'mdt_vae_enc_prologue_f32': [vp, i32, i32, vp, i32, i32, i32],
     'mdt_lds_poison': [vp],
     'mdt_gemm_f32': [C.POINTER(GemmF32Args)],
     'mdt_gemm_bf16x3': [C.POINTER(GemmF32Args)],
@@ -121,6 +125,7 @@ _PLAIN = {
     'mdt_nt8o_report': [C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), i32],
     'mdt_nt8o_stamps': [C.POINTER(C.c_uint64)],
     'mdt_attn_f32_ws_floats': [i32, i32, i32, i32],
+    'mdt_gn_stats_ordered_ws_floats': [i32, i32],
 }
 EXPORTED = sorted(list(_PROTOS) + list(_PLAIN) + ['mdt_last_error', 'mdt_version'])
 ABI_VERSION = 4  # == MDT_ABI_VERSION of include/maskdit_hip.h (tests/test_capi_cpu.py compares the two)
@@ -185,7 +190,7 @@ def lib():
     for name, argt in _PLAIN.items():
         fn = getattr(L, name)
         fn.argtypes = argt
-        fn.restype = i64 if name == 'mdt_attn_f32_ws_floats' else i32
+        fn.restype = i64 if name.endswith('_ws_floats') else i32
     L.mdt_last_error.restype = C.c_char_p
     L.mdt_last_error.argtypes = []
     L.mdt_version.restype = i32

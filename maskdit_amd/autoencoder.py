@@ -26,7 +26,17 @@ moments [B, 8, R/8, R/8] fp32, for R = 128, 256, 512.  The Encoder (:212-304) ru
 (GroupNorm + swish writer, implicit-GEMM 3x3 convolutions with the fused epilogue, 1x1 GEMMs, the mid-block attention)
 plus three entries of its own: mdt_vae_enc_prologue (image -> conv_in's im2col, optional x mirror),
 mdt_conv3x3_down_nhwc (Downsample: pad (0, 1, 0, 1) + stride-2 convolution) and mdt_vae_enc_epilogue (quant_conv ->
-NCHW moments).  bf16 operands, fp32 accumulation, like decode."""
+NCHW moments).  bf16 operands, fp32 accumulation, like decode.
+
+PRECISION.  Everything above is `precision='bf16'`, the default.  The reference runs its autoencoder in fp32;
+`get_model(path, precision='bf16x3')` / `vae.set_precision('bf16x3')` select that accuracy for decode and encode: fp32
+weights and fp32 operands (mdt_gn_im2col_f32 / mdt_vae_enc_prologue_f32, exact-form GroupNorm + swish), every 3x3
+convolution one implicit GEMM in the three-term split arithmetic of the sampler's 'bf16x3' plan (mdt_conv3x3_bf16x3_nhwc:
+any image side, any batch), 1x1 convolutions and the two im2col convolutions on mdt_gemm_bf16x3, attention scores and P V on
+the exact-fp32 mdt_gemm_f32 around mdt_softmax_rows_f32, GroupNorm sums from mdt_gn_stats_ordered (fixed summation order:
+no atomics anywhere on this path, two runs give identical bits).  MDT_VAE_X3_IM2COL=1
+forces the stride-1 3x3 convolutions through a materialised fp32 im2col matrix + mdt_gemm_bf16x3 instead (the comparison
+route of tools/vae_bf16x3_bench.py; 9x the activation bytes, small batches only)."""
 from __future__ import annotations
 
 import os
@@ -44,6 +54,9 @@ ENC_SIDES = (128, 256, 512)   # image sides encode_moments accepts
 FUSE_EPILOGUE = os.environ.get('MDT_VAE_FUSE', '1') != '0'  # A/B switch (see _conv)
 # widest convolution (output channels) that takes the fused epilogue: it exists for 128-column tiles only (the 256-wide
 # kernel spills with it), so for 256 / 512 channels fusing trades a ~15-20 % slower GEMM against the saved passes
+PRECISIONS = ('bf16', 'bf16x3')
+X3_FORCE_IM2COL = os.environ.get('MDT_VAE_X3_IM2COL', '0') == '1'  # A/B switch of the 'bf16x3' arithmetic (see _conv_x3)
+X3_ZLINE = 32  # floats of zeros in front of every fp32 workspace buffer: the padding taps of mdt_conv3x3_bf16x3_nhwc read them
 FUSE_MAX_COUT = int(os.environ.get('MDT_VAE_FUSE_MAXC', '256'))  # measured at batch 64: 128 -> 62.4 ms, 256 -> 61.7, 512 -> 64.4, off -> 67.4
 
 
@@ -139,8 +152,11 @@ class FrozenAutoencoderKL(nn.Module):
     """Counterpart of autoencoder.py:412-466: decode-only by default; `encoder=True` adds the encoder + quant_conv
     weights (all of autoencoder_kl.pth, loaded strictly) and the encode side."""
 
-    def __init__(self, pretrained_path: Optional[str] = None, scale_factor: float = 0.18215, encoder: bool = False):
+    def __init__(self, pretrained_path: Optional[str] = None, scale_factor: float = 0.18215, encoder: bool = False,
+                 precision: str = 'bf16'):
         super().__init__()
+        self._packed_x3: Optional[dict] = None
+        self.set_precision(precision)
         self.scale_factor = scale_factor
         self.embed_dim = Z_CH
         self.has_encoder = bool(encoder)
@@ -156,6 +172,13 @@ class FrozenAutoencoderKL(nn.Module):
             sd = torch.load(pretrained_path, map_location='cpu')
             self.load_state_dict(sd)
         self.eval()
+
+    def set_precision(self, precision: str):
+        """'bf16' (default): bf16 operands, fp32 accumulation.  'bf16x3': the reference's fp32 accuracy (module docstring)."""
+        if precision not in PRECISIONS:
+            raise ValueError(f'maskdit_amd.autoencoder: precision {precision!r} is not one of {PRECISIONS}')
+        self.precision = precision
+        return self
 
     # ---- state dict under the reference's dotted names ------------------------------------
     def named_weights(self):
@@ -181,10 +204,12 @@ class FrozenAutoencoderKL(nn.Module):
                         raise RuntimeError(f'{k}: shape {tuple(sd[k].shape)} != {tuple(p.shape)}')
                     p.copy_(sd[k])
         self._packed = None
+        self._packed_x3 = None
         return missing, unexpected
 
     def _apply(self, fn, *a, **k):
         self._packed = None
+        self._packed_x3 = None
         self._wdict = None
         self._act_zeroed = None
         self._ws.clear()
@@ -353,6 +378,188 @@ class FrozenAutoencoderKL(nn.Module):
         ops.gemm_nt(o, wp, bp, ops.EPI_F32, outf=proj)
         return self._add(x, proj, slot)
 
+    # ---- the 'bf16x3' arithmetic (module docstring, PRECISION) --------------------------------------
+    def _pack_x3(self):
+        """conv weight [Cout, Cin, k, k] -> fp32 [Cout, K], K ordered (ky, kx, cin) like `_pack` and zero-padded to a multiple
+        of 4 (the encoder's conv_in: 27 -> 28); no padding of Cout.  The attention value bias is folded into the output
+        projection's, as in `_pack` (in fp64, rounded once).  Built when 'bf16x3' is first used, dropped by `_apply`."""
+        W = dict(self.named_weights())
+        pk = {}
+        for name, p in W.items():
+            if name.endswith('.weight') and p.dim() == 4:
+                base = name[:-len('.weight')]
+                cout, cin, k, _ = p.shape
+                K = _rup(k * k * cin, 4)
+                m = torch.zeros(cout, K, device=p.device, dtype=torch.float32)
+                m[:, :k * k * cin] = p.detach().permute(0, 2, 3, 1).reshape(cout, -1)
+                pk[base] = (m, W[base + '.bias'].detach().to(torch.float32).contiguous(), K, cout)
+        for a in ('decoder.mid.attn_1', 'encoder.mid.attn_1') if self.has_encoder else ('decoder.mid.attn_1',):
+            wp = W[a + '.proj_out.weight'].detach().reshape(W[a + '.proj_out.weight'].shape[0], -1).double()
+            beff = (W[a + '.proj_out.bias'].detach().double() + wp @ W[a + '.v.bias'].detach().double()).float()
+            m, _, K, cout = pk[a + '.proj_out']
+            pk[a + '.proj_out'] = (m, beff.contiguous(), K, cout)
+        self._packed_x3 = pk
+        return pk
+
+    def _fbuf(self, key, shape):
+        """fp32 workspace behind X3_ZLINE zero floats (written once, at allocation; no kernel stores in front of its output),
+        so that every activation of the 'bf16x3' path can be the `act` argument of mdt_conv3x3_bf16x3_nhwc as it is"""
+        n = 1
+        for s in shape:
+            n *= s
+        t = self._ws.get(key)
+        if t is None or t.numel() < X3_ZLINE + n:
+            t = torch.zeros(X3_ZLINE + n, device=next(self.parameters()).device, dtype=torch.float32)
+            self._ws[key] = t
+        return t[X3_ZLINE:X3_ZLINE + n].view(shape)
+
+    def _sums_x3(self, x, B, HW, c):
+        """GroupNorm sums [B, 32, 2] of x in a fixed summation order (mdt_gn_stats_ordered; mdt_gn_stats combines its pixel
+        chunks with atomics, which made two decodes differ in the last bits)"""
+        sums = self._fbuf('x3_sums', (B, GROUPS, 2))
+        ws = self._fbuf('x3_sums_ws', (int(_lib.lib().mdt_gn_stats_ordered_ws_floats(B, GROUPS)),))
+        call('mdt_gn_stats_ordered', x.data_ptr(), sums.data_ptr(), ws.data_ptr(), B, HW, c, GROUPS, ops.stream_ptr())
+        return sums
+
+    def _conv_x3(self, x, B, H, cin, name, k=3, norm=None, swish=False, up=0, slot='a', res=None, down=0):
+        """x: fp32 [B*H*H, cin] (NHWC, from `_fbuf`) -> fp32 [B*Ho*Ho, ldo], ldo = Cout rounded up to 4; `res` (same shape) is
+        added in the epilogue.  3x3 with cin % 32 == 0: the implicit GEMM, on x itself where there is no GroupNorm / swish in
+        front; conv_in (4 / 3 input channels) and, under MDT_VAE_X3_IM2COL=1, every stride-1 3x3: materialised im2col +
+        mdt_gemm_bf16x3 (the stride-2 Downsample has no im2col writer and stays implicit); 1x1: mdt_gemm_bf16x3."""
+        st = ops.stream_ptr()
+        wmat, bias, K, cout = self._packed_x3[name]
+        Ho = H >> 1 if down else H << up
+        M = B * Ho * Ho
+        ldo = _rup(cout, 4)
+        assert res is None or tuple(res.shape) == (M, ldo)
+        out = self._fbuf('x3_out_' + slot, (M, ldo))
+        sums = gamma = beta = None
+        if norm is not None:
+            sums = self._sums_x3(x, B, H * H, cin)
+            W = self._weights()
+            gamma, beta = W[norm + '.weight'], W[norm + '.bias']
+
+        def write(dst, ksize, upv, Kp):
+            call('mdt_gn_im2col_f32', x.data_ptr(), sums.data_ptr() if sums is not None else None,
+                 gamma.data_ptr() if gamma is not None else None, beta.data_ptr() if beta is not None else None, dst.data_ptr(),
+                 B, H, H, cin, GROUPS, ksize, upv, int(swish), Kp, st)
+
+        pointwise = norm is not None or swish
+        if k == 3 and cin % 32 == 0 and (down or not X3_FORCE_IM2COL):
+            act = x
+            if pointwise:
+                act = self._fbuf('x3_act', (B * H * H, cin))
+                write(act, 1, 0, cin)
+            call('mdt_conv3x3_bf16x3_nhwc', act.data_ptr(), B, H, cin, up, down, wmat.data_ptr(), bias.data_ptr(),
+                 res.data_ptr() if res is not None else None, out.data_ptr(), ldo, cout, st)
+            return out
+        if k == 3:
+            a = self._fbuf('x3_col', (M, K))
+            write(a, 3, up, K)
+        elif pointwise:
+            a = self._fbuf('x3_act', (M, cin))
+            write(a, 1, 0, cin)
+        else:
+            a = x
+        ops.gemm_bf16x3(a, wmat, out, M, cout, K, lda=K, ldb=K, ldo=ldo, bias=bias,
+                        epi=ops.F32EPI_GATE_RES if res is not None else ops.F32EPI_NONE, res=res, rows_per_sample=1)
+        return out
+
+    def _res_x3(self, x, B, H, cin, cout, name, slot):
+        h = self._conv_x3(x, B, H, cin, name + '.conv1', norm=name + '.norm1', swish=True, slot='h1')
+        if cin != cout:
+            x = self._conv_x3(x, B, H, cin, name + '.nin_shortcut', k=1, slot='sc')
+        return self._conv_x3(h, B, H, cout, name + '.conv2', norm=name + '.norm2', swish=True, slot=slot, res=x)
+
+    def _attn_x3(self, x, B, H, c, name, slot):
+        """AttnBlock (autoencoder.py:165-200): q / k / v / proj_out on mdt_gemm_bf16x3, scores and P V in exact fp32, batched
+        over as many images as keep the score buffer within 256 MiB."""
+        st = ops.stream_ptr()
+        W = self._weights()
+        T = H * H
+        sums = self._sums_x3(x, B, T, c)
+        hn = self._fbuf('x3_act', (B * T, c))
+        call('mdt_gn_im2col_f32', x.data_ptr(), sums.data_ptr(), W[name + '.norm.weight'].data_ptr(), W[name + '.norm.bias'].data_ptr(),
+             hn.data_ptr(), B, H, H, c, GROUPS, 1, 0, 0, c, st)
+        qkv = []
+        for n in 'qkv':
+            wmat, bias, K, cout = self._packed_x3[f'{name}.{n}']
+            t = self._fbuf('x3_attn_' + n, (B * T, c))
+            ops.gemm_bf16x3(hn, wmat, t, B * T, c, c, bias=None if n == 'v' else bias)  # (v bias folded into proj_out's)
+            qkv.append(t)
+        q, k, v = qkv
+        o = self._fbuf('x3_attn_o', (B * T, c))
+        nb = max(1, min(B, (1 << 26) // (T * T)))
+        S = self._fbuf('x3_attn_S', (nb * T, T))
+        for b0 in range(0, B, nb):
+            n = min(nb, B - b0)
+            off = b0 * T * c
+            ops.gemm_f32(q, k, S, T, T, c, lda=c, ldb=c, ldo=T, batch=n, heads=1, a_strides=(T * c, 0), b_strides=(T * c, 0),
+                         o_strides=(T * T, 0), a_off=off, b_off=off)                       # w_[i, j] = q_i . k_j   (:186)
+            call('mdt_softmax_rows_f32', S.data_ptr(), n * T, T, T, float(c) ** -0.5, st)  # :187-188
+            ops.gemm_f32(S, v, o, T, c, T, lda=T, ldb=c, ldo=c, b_kmajor=True, batch=n, heads=1, a_strides=(T * T, 0),
+                         b_strides=(T * c, 0), o_strides=(T * c, 0), b_off=off, o_off=off)  # h_[i, :] = sum_j P[i, j] v_j
+        wp, bp, _, _ = self._packed_x3[name + '.proj_out']
+        out = self._fbuf('x3_out_' + slot, (B * T, c))
+        ops.gemm_bf16x3(o, wp, out, B * T, c, c, bias=bp, epi=ops.F32EPI_GATE_RES, res=x, rows_per_sample=1)
+        return out
+
+    def _decode_x3(self, z, B, R):
+        st = ops.stream_ptr()
+        W = self._weights()
+        if self._packed_x3 is None:
+            self._pack_x3()
+        x = self._fbuf('x3_x0', (B * R * R, Z_CH))
+        call('mdt_vae_prologue', z.data_ptr(), W['post_quant_conv.weight'].data_ptr(), W['post_quant_conv.bias'].data_ptr(),
+             x.data_ptr(), B, R * R, float(self.scale_factor), st)
+        c = CH * CH_MULT[-1]
+        H = R
+        x = self._conv_x3(x, B, H, Z_CH, 'decoder.conv_in', slot='x1')
+        x = self._res_x3(x, B, H, c, c, 'decoder.mid.block_1', 'p')
+        x = self._attn_x3(x, B, H, c, 'decoder.mid.attn_1', 'q')
+        x = self._res_x3(x, B, H, c, c, 'decoder.mid.block_2', 'p')
+        flip = 1
+        for i_level in reversed(range(len(CH_MULT))):
+            cout = CH * CH_MULT[i_level]
+            for j in range(NUM_RES_BLOCKS + 1):
+                x = self._res_x3(x, B, H, c, cout, f'decoder.up.{i_level}.block.{j}', 'pq'[flip])
+                flip ^= 1
+                c = cout
+            if i_level != 0:
+                x = self._conv_x3(x, B, H, c, f'decoder.up.{i_level}.upsample.conv', up=1, slot='u')
+                H *= 2
+        y = self._conv_x3(x, B, H, c, 'decoder.conv_out', norm='decoder.norm_out', swish=True, slot='a')
+        img = torch.empty(B, OUT_CH, H, H, device=z.device, dtype=torch.float32)
+        call('mdt_vae_epilogue', y.data_ptr(), y.shape[1], img.data_ptr(), B, H * H, OUT_CH, st)
+        return img
+
+    def _encode_chunk_x3(self, x, u8, flip, mom):
+        st = ops.stream_ptr()
+        W = self._weights()
+        B = x.shape[0]
+        R = x.shape[1] if u8 else x.shape[2]
+        wmat, bias, K, cout = self._packed_x3['encoder.conv_in']
+        col = self._fbuf('x3_col', (B * R * R, K))
+        call('mdt_vae_enc_prologue_f32', x.data_ptr(), int(u8), int(bool(flip)), col.data_ptr(), B, R, K, st)
+        h = self._fbuf('x3_out_x1', (B * R * R, cout))
+        ops.gemm_bf16x3(col, wmat, h, B * R * R, cout, K, bias=bias)
+        H, c, sl = R, CH, 0
+        for i_level in range(len(CH_MULT)):
+            cout = CH * CH_MULT[i_level]
+            for j in range(NUM_RES_BLOCKS):
+                h = self._res_x3(h, B, H, c, cout, f'encoder.down.{i_level}.block.{j}', 'pq'[sl])
+                sl ^= 1
+                c = cout
+            if i_level != len(CH_MULT) - 1:
+                h = self._conv_x3(h, B, H, c, f'encoder.down.{i_level}.downsample.conv', down=1, slot='u')
+                H //= 2
+        h = self._res_x3(h, B, H, c, c, 'encoder.mid.block_1', 'pq'[sl])
+        h = self._attn_x3(h, B, H, c, 'encoder.mid.attn_1', 'pq'[sl ^ 1])
+        h = self._res_x3(h, B, H, c, c, 'encoder.mid.block_2', 'pq'[sl])
+        y = self._conv_x3(h, B, H, c, 'encoder.conv_out', norm='encoder.norm_out', swish=True, slot='a')
+        call('mdt_vae_enc_epilogue', y.data_ptr(), y.shape[1], W['quant_conv.weight'].data_ptr(), W['quant_conv.bias'].data_ptr(),
+             mom.data_ptr(), B, H * H, st)
+
     # ---- public surface -----------------------------------------------------------------------
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
@@ -361,8 +568,6 @@ class FrozenAutoencoderKL(nn.Module):
             raise _lib.MaskDiTLibError('maskdit_amd.autoencoder: z is not on a HIP device; there is no CPU path')
         if next(self.parameters()).device != z.device:
             raise _lib.MaskDiTLibError('maskdit_amd.autoencoder: call .to(z.device) first')
-        if self._packed is None:
-            self._pack()
         z = z.to(torch.float32).contiguous()
         B, C, R, R2 = z.shape
         assert C == Z_CH and R == R2 and R % 8 == 0, f'latent shape {tuple(z.shape)}'
@@ -370,6 +575,10 @@ class FrozenAutoencoderKL(nn.Module):
             # the mid-block attention runs its T x T score GEMMs through mdt_gemm_nt (N % 128) and mdt_softmax_rows
             # (<= 4096 keys): R = 16, 32, 48, 64 (128 .. 512 px images; the shipped configs use 32 and 64)
             raise NotImplementedError(f'maskdit_amd.autoencoder: latent side {R} unsupported (R * R must be a multiple of 128, <= 4096)')
+        if self.precision == 'bf16x3':
+            return self._decode_x3(z, B, R)
+        if self._packed is None:
+            self._pack()
         st = ops.stream_ptr()
         W = self._weights()
         x = self._buf('x0', (B * R * R, Z_CH), torch.float32)
@@ -430,12 +639,15 @@ class FrozenAutoencoderKL(nn.Module):
             # implicit GEMM on power-of-two sides; 384 (and any other side) is outside what this encoder covers
             raise NotImplementedError(f'maskdit_amd.autoencoder: image side {R}x{R2} unsupported (square, one of {ENC_SIDES})')
         x = x.contiguous()
-        if self._packed is None:
+        x3 = self.precision == 'bf16x3'
+        if x3 and self._packed_x3 is None:
+            self._pack_x3()
+        if not x3 and self._packed is None:
             self._pack()
         mom = torch.empty(B, 2 * Z_CH, R // 8, R // 8, device=x.device, dtype=torch.float32)
-        n = self.encode_chunk(R)
+        n = self.encode_chunk(R)  # ('bf16x3' has no addressing limit of its own; the same chunks bound its workspace)
         for s in range(0, B, n):
-            self._encode_chunk(x[s:s + n], u8, flip, mom[s:s + n])
+            (self._encode_chunk_x3 if x3 else self._encode_chunk)(x[s:s + n], u8, flip, mom[s:s + n])
         return mom
 
     def _encode_chunk(self, x, u8, flip, mom):
@@ -510,7 +722,8 @@ def synthetic_state_dict(seed: int = 0, encoder: bool = True) -> Dict[str, torch
     return sd
 
 
-def get_model(pretrained_path: Optional[str], scale_factor: float = 0.18215, encoder: bool = False) -> FrozenAutoencoderKL:
+def get_model(pretrained_path: Optional[str], scale_factor: float = 0.18215, encoder: bool = False,
+              precision: str = 'bf16') -> FrozenAutoencoderKL:
     """autoencoder.py:468-474 (`pretrained_path=None`: zero weights, to be filled with load_state_dict; `encoder=True`:
-    the encode side as well)."""
-    return FrozenAutoencoderKL(pretrained_path, scale_factor, encoder=encoder)
+    the encode side as well; `precision`: 'bf16' or the fp32-accurate 'bf16x3')."""
+    return FrozenAutoencoderKL(pretrained_path, scale_factor, encoder=encoder, precision=precision)

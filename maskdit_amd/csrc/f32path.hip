@@ -672,6 +672,156 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_kernel(const Params p, const 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The autoencoder's 3x3 convolutions in the bf16x3 arithmetic, as an IMPLICIT GEMM: gemm_bf16x3_kernel (same tile, same
+// split while staging, same six products on two accumulators, same epilogue -- its body restated, so that kernel's code does
+// not change) whose A operand is gathered from the fp32 NHWC activation [B, Hi, Hi, C] instead of read from a matrix.  Row m
+// of the product is output pixel (b, yo, xo); K runs over (ky, kx, c) and C % 32 == 0, so a 32-wide K-tile lies inside ONE
+// tap.  A thread stages one 8-float chunk of ONE A row per K-tile: (b, yo, xo) are computed once, per K-tile only the tap
+// changes, which gives a source pixel or -- for a padding tap -- the zero line of 32 floats in front of `act` (selected through
+// the ADDRESS, so no load is followed by a select that would wait for it).  Row bases are 64-bit: no batch limit below
+// M = B Ho Ho < 2^31.  Gather modes (geometry of mdt_conv3x3_nhwc / mdt_conv3x3_down_nhwc):
+//   plain  mul 1, pad 1, sh 0: source (yo + ky - 1, xo + kx - 1), inside [0, Hi)
+//   up     mul 1, pad 1, sh 1: the same in the nearest-2x image of side 2 Hi, source pixel = coordinate >> 1
+//   down   mul 2, pad 0, sh 0: source (2 yo + ky, 2 xo + kx), row / column Hi reading zero (F.pad (0, 1, 0, 1), stride 2)
+// B is the fp32 weight [Cout][9 C]; rows beyond M / N are clamped (never stored).  No atomics, no split-K.
+struct ConvGeom {
+  int Hi, C, Ho;        // input side, input channels, output side
+  int mul, pad, sh;     // source coordinate = (out * mul + tap - pad), valid inside [0, lim), source pixel = coordinate >> sh
+  int lim;
+};
+
+__global__ __launch_bounds__(512) void conv3x3_bf16x3_kernel(const Params p, const ConvGeom cg, const int tiles_m, const int tiles_n) {
+  constexpr int NT = 512, WN = 4, MB = 2, NB = 1, BM = 128, BN = 128, BKT = 32;
+  constexpr int CPR = BKT / 8;
+  constexpr int PLANE = (BM + BN) * CPR;
+  static_assert(BM * CPR == NT && BN * CPR == NT, "one A chunk and one B chunk per thread and K-tile");
+  __shared__ __attribute__((aligned(16))) u32x4 lds[2][3][PLANE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const int nt = tiles_m * tiles_n;
+  int t = blockIdx.x;
+  {
+    const int q = nt >> 3, r = nt & 7, x = t & 7, i = t >> 3;
+    t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
+  }
+  constexpr int GM = 8;
+  const int per_group = GM * tiles_n, grp = t / per_group, first_m = grp * GM;
+  const int gm = min(tiles_m - first_m, GM), in_g = t - grp * per_group;
+  const int tm = first_m + in_g % gm, tn = in_g / gm;
+  const int m0 = tm * BM, n0 = tn * BN;
+
+  f32x16 acc[MB][NB], cor[MB][NB];
+#pragma unroll
+  for (int i = 0; i < MB; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = cor[i][j][e] = 0.f;
+
+  // this thread's chunk: tile row tid / CPR, floats 8 (tid % CPR) .. + 7 of the K-tile, of A (gathered) and of B
+  const int srow = tid / CPR, sc = tid % CPR;
+  const int m = min(m0 + srow, p.M - 1);
+  const int hw = cg.Ho * cg.Ho;
+  const int b = m / hw, pix = m - b * hw;
+  const int yo = pix / cg.Ho, xo = pix - yo * cg.Ho;
+  const int ybase = yo * cg.mul - cg.pad, xbase = xo * cg.mul - cg.pad;
+  const float* const abase = p.A + (long)b * cg.Hi * cg.Hi * cg.C + 8 * sc;   // sample b, channel chunk of this thread
+  const float* const azero = p.A - BKT + 8 * sc;                               // the zero line in front of the activation
+  const float* const pb = p.B + (long)min(n0 + srow, p.N - 1) * p.ldb + 8 * sc;
+  f32x4 g[2][2];
+  int tap = 0, c0 = 0;  // (ky, kx) = (tap / 3, tap % 3) and first channel of the NEXT K-tile to load (wave-uniform)
+  auto gload = [&](int k0) X3_INLINE {
+    const int ky = (tap * 11) >> 5, kx = tap - 3 * ky;  // tap / 3 for tap < 9
+    const int yy = ybase + ky, xx = xbase + kx;
+    const bool ok = (unsigned)yy < (unsigned)cg.lim && (unsigned)xx < (unsigned)cg.lim;
+    const float* src = ok ? abase + ((long)((yy >> cg.sh) * cg.Hi + (xx >> cg.sh)) * cg.C + c0) : azero;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      g[0][h] = *(const f32x4*)(src + 4 * h);
+      g[1][h] = *(const f32x4*)(pb + k0 + 4 * h);
+    }
+    c0 += BKT;
+    if (c0 == cg.C) {
+      c0 = 0;
+      ++tap;
+    }
+  };
+  auto lstore = [&](int buf) X3_INLINE {
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const int row = srow + o * BM;
+      const int at = row * CPR + (sc ^ ((row >> 2) & 3));
+      u32x4 w0, w1, w2;
+      x3_split8(g[o][0], g[o][1], w0, w1, w2);
+      lds[buf][0][at] = w0;
+      lds[buf][1][at] = w1;
+      lds[buf][2][at] = w2;
+    }
+  };
+
+  const int nk = p.K / BKT;
+  const int r = lane & 31, kh = lane >> 5;
+  bf16x8 fa[3][MB], fb[3][NB];
+  auto fload = [&](int buf, int s) X3_INLINE {
+#pragma unroll
+    for (int i = 0; i < MB; ++i) {
+      const int row = (wm * MB + i) * 32 + r;
+      const int at = row * CPR + ((2 * s + kh) ^ ((row >> 2) & 3));
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) fa[pl][i] = __builtin_bit_cast(bf16x8, lds[buf][pl][at]);
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int row = BM + (wn * NB + i) * 32 + r;
+      const int at = row * CPR + ((2 * s + kh) ^ ((row >> 2) & 3));
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) fb[pl][i] = __builtin_bit_cast(bf16x8, lds[buf][pl][at]);
+    }
+  };
+  auto fmma = [&]() X3_INLINE {
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+      for (int jj = 0; jj < NB; ++jj) acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[0][jj], fa[0][i], acc[i][jj], 0, 0, 0);
+    constexpr int PB[5] = {0, 1, 0, 1, 2}, PA[5] = {1, 0, 2, 1, 0};
+#pragma unroll
+    for (int pr = 0; pr < 5; ++pr)
+#pragma unroll
+      for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int jj = 0; jj < NB; ++jj)
+          cor[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[PB[pr]][jj], fa[PA[pr]][i], cor[i][jj], 0, 0, 0);
+  };
+  // the K loop of gemm_bf16x3_kernel (hipcc counts the waits)
+  auto step = [&](auto par_c, int kt) X3_INLINE {
+    constexpr int par = decltype(par_c)::value;
+    const bool more = kt + 1 < nk;
+    if (more) gload((kt + 1) * BKT);
+#pragma unroll
+    for (int s = 0; s < BKT / 16; ++s) {
+      fload(par, s);
+      fmma();
+    }
+    if (more) lstore(par ^ 1);
+    __syncthreads();
+  };
+  gload(0);
+  lstore(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; kt += 2) {
+    step(std::integral_constant<int, 0>{}, kt);
+    if (kt + 1 < nk) step(std::integral_constant<int, 1>{}, kt + 1);
+  }
+#pragma unroll
+  for (int i = 0; i < MB; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] += x3_finite(acc[i][j][e]) ? cor[i][j][e] : 0.f;
+  f32_epilogue<MB, NB>(p, acc, m0, n0, wm, wn, r, kh, p.out);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void softmax_rows_f32_kernel(float* __restrict__ s, long R, int n, int n_valid, float scale) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -951,6 +1101,34 @@ extern "C" int mdt_gemm_bf16x3(const mdt_gemm_f32_args* a, mdt_stream_t stream) 
   const f32p::Params p = f32_params(a, 1);
   hipLaunchKernelGGL(f32p::gemm_bf16x3_kernel, dim3((unsigned)(tm * tn)), dim3(512), 0, (hipStream_t)stream, p, (int)tm, (int)tn);
   return mdt_check_launch("gemm_bf16x3");
+}
+
+// The autoencoder's 3x3 convolutions of the 'bf16x3' arithmetic (conv3x3_bf16x3_kernel).
+extern "C" int mdt_conv3x3_bf16x3_nhwc(const float* act, int B, int Hi, int C, int up, int down, const float* W, const float* bias,
+                                       const float* res, float* out, long ldo, int Cout, mdt_stream_t stream) {
+  MDT_REQUIRE(act && W && out, "conv3x3_bf16x3: null pointer");
+  MDT_REQUIRE(B > 0 && Hi > 0 && Cout > 0 && C >= 32 && C % 32 == 0, "conv3x3_bf16x3: B, Hi, Cout > 0 and C a positive multiple of 32");
+  MDT_REQUIRE((up == 0 || up == 1) && (down == 0 || down == 1) && !(up && down), "conv3x3_bf16x3: up and down are 0 or 1, not both");
+  MDT_REQUIRE(!down || Hi % 2 == 0, "conv3x3_bf16x3: the stride-2 form needs an even input side");
+  MDT_REQUIRE(Hi <= 16384 && 9L * C <= 2147483647L, "conv3x3_bf16x3: image side / channel count too large");
+  MDT_REQUIRE(ldo >= Cout, "conv3x3_bf16x3: ldo < Cout");
+  MDT_REQUIRE((((uintptr_t)act | (uintptr_t)W) & 15) == 0, "conv3x3_bf16x3: act and W must be 16-byte aligned");
+  const int Ho = down ? Hi / 2 : Hi << up;
+  const long M = (long)B * Ho * Ho;
+  MDT_REQUIRE(M <= 2147483647L, "conv3x3_bf16x3: B * Ho * Ho must fit 31 bits");
+  const long tm = cdiv(M, 128), tn = cdiv(Cout, 128);
+  MDT_REQUIRE(tm * tn <= 2147483647L, "conv3x3_bf16x3: too many tiles");
+  mdt_gemm_f32_args a = {};
+  a.A = act; a.lda = C; a.B = W; a.ldb = 9L * C;
+  a.M = (int)M; a.N = Cout; a.K = 9 * C;
+  a.bias = bias; a.epi = res ? MDT_F32EPI_GATE_RES : MDT_F32EPI_NONE;  // gate NULL = 1: out = res + (acc + bias)
+  a.out = out; a.ldo = ldo; a.res = res; a.ldres = ldo; a.rows_per_sample = 1;
+  const f32p::Params p = f32_params(&a, 1);
+  f32p::ConvGeom cg;
+  cg.Hi = Hi; cg.C = C; cg.Ho = Ho;
+  cg.mul = down ? 2 : 1; cg.pad = down ? 0 : 1; cg.sh = up; cg.lim = down ? Hi : Ho;
+  hipLaunchKernelGGL(f32p::conv3x3_bf16x3_kernel, dim3((unsigned)(tm * tn)), dim3(512), 0, (hipStream_t)stream, p, cg, (int)tm, (int)tn);
+  return mdt_check_launch("conv3x3_bf16x3");
 }
 
 extern "C" int mdt_gemm_f32(const mdt_gemm_f32_args* a, mdt_stream_t stream) {

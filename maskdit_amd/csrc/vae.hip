@@ -238,6 +238,193 @@ __global__ __launch_bounds__(256) void vae_enc_epilogue_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------
+// GroupNorm statistics in a FIXED summation order (the 'bf16x3' arithmetic must give identical bits on every run;
+// gn_stats_kernel combines its pixel chunks with fp32 atomics, in whatever order the workgroups finish).  The same
+// per-workgroup sums as gn_stats_kernel, stored as partials [b, chunk, g, 2]; a second launch folds the chunks of one
+// (sample, group) in index order, in fp64.
+__global__ __launch_bounds__(256) void gn_stats_part_kernel(const float* __restrict__ x, float* __restrict__ part, int HW, int C,
+                                                            int groups, int px_per_block) {
+  __shared__ float red[2][256];
+  const int b = blockIdx.y;
+  const int quads = C >> 2;
+  const int lanes = 256 / quads;
+  const int q = threadIdx.x % quads, pl = threadIdx.x / quads;
+  const int p0 = blockIdx.x * px_per_block, p1 = min(p0 + px_per_block, HW);
+  float s = 0.f, ss = 0.f;
+  if (pl < lanes) {
+    const float* base = x + ((long)b * HW) * C + 4 * q;
+    for (int p = p0 + pl; p < p1; p += lanes) {
+      const f32x4 v = *(const f32x4*)(base + (long)p * C);
+      s += v[0] + v[1] + v[2] + v[3];
+      ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+    }
+  }
+  red[0][threadIdx.x] = s;
+  red[1][threadIdx.x] = ss;
+  __syncthreads();
+  const int qpg = (C / groups) >> 2;
+  if (threadIdx.x < groups) {
+    const int g = threadIdx.x;
+    float a = 0.f, c = 0.f;
+    for (int l = 0; l < lanes; ++l)
+      for (int k = 0; k < qpg; ++k) {
+        a += red[0][l * quads + g * qpg + k];
+        c += red[1][l * quads + g * qpg + k];
+      }
+    float* o = part + (((long)b * gridDim.x + blockIdx.x) * groups + g) * 2;
+    o[0] = a;
+    o[1] = c;
+  }
+}
+
+__global__ __launch_bounds__(256) void gn_stats_fold_kernel(const float* __restrict__ part, float* __restrict__ sums, int chunks,
+                                                            int groups) {
+  const int b = blockIdx.x, g = threadIdx.x;
+  if (g >= groups) return;
+  double a = 0.0, c = 0.0;
+  for (int k = 0; k < chunks; ++k) {
+    const float* i = part + (((long)b * chunks + k) * groups + g) * 2;
+    a += (double)i[0];
+    c += (double)i[1];
+  }
+  sums[((long)b * groups + g) * 2] = (float)a;
+  sums[((long)b * groups + g) * 2 + 1] = (float)c;
+}
+
+// ------------------------------------------------------------------------------------------
+// The operand writers of the 'bf16x3' autoencoder arithmetic: the two kernels above with fp32 results and exact-form
+// pointwise functions (IEEE division / sqrt / expf instead of the 1-ulp hardware forms whose error the bf16 rounding hid).
+// One thread = 4 consecutive floats of one output row: 4 channels of one tap (C % 4 == 0), which lie in one GroupNorm
+// group wherever C / groups is a multiple of 4.
+__device__ __forceinline__ float swish_f32(float x) { return x / (1.f + expf(-x)); }
+
+__global__ __launch_bounds__(256) void gn_im2col_f32_kernel(const float* __restrict__ x, const float* __restrict__ sums,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float* __restrict__ col, int B, int H, int W, int C, int groups,
+                                                            int ks, int up, int swish, int Kp, float inv_n) {
+  const int Ho = H << up, Wo = W << up;
+  const int chunks = Kp >> 2;
+  const long total = (long)B * Ho * Wo * chunks;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int ch = (int)(idx % chunks);
+  const long row = idx / chunks;
+  const int xo = (int)(row % Wo);
+  const int yo = (int)((row / Wo) % Ho);
+  const int b = (int)(row / ((long)Wo * Ho));
+  const int k0 = ch * 4;
+  f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
+  if (k0 < ks * ks * C) {
+    const int tap = k0 / C, c0 = k0 - tap * C, pad = ks >> 1;
+    const int yy = yo + tap / ks - pad, xx = xo + tap % ks - pad;  // coordinates in the (up-sampled) input image
+    if (yy >= 0 && yy < Ho && xx >= 0 && xx < Wo) {
+      const f32x4 v4 = *(const f32x4*)(x + (((long)b * H + (yy >> up)) * W + (xx >> up)) * C + c0);
+      float v[4] = {v4[0], v4[1], v4[2], v4[3]};
+      if (sums) {
+        const int cpg = C / groups;
+        const f32x4 ga = *(const f32x4*)(gamma + c0), be = *(const f32x4*)(beta + c0);
+        if (cpg % 4 == 0) {
+          const float2 sq = *(const float2*)(sums + ((long)b * groups + c0 / cpg) * 2);
+          const float mean = sq.x * inv_n;
+          const float rstd = 1.f / sqrtf(fmaxf(sq.y * inv_n - mean * mean, 0.f) + 1e-6f);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = (v[e] - mean) * rstd * ga[e] + be[e];
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float* sg = sums + ((long)b * groups + (c0 + e) / cpg) * 2;
+            const float mean = sg[0] * inv_n;
+            v[e] = (v[e] - mean) / sqrtf(fmaxf(sg[1] * inv_n - mean * mean, 0.f) + 1e-6f) * ga[e] + be[e];
+          }
+        }
+      }
+      if (swish) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = swish_f32(v[e]);
+      }
+      o = (f32x4){v[0], v[1], v[2], v[3]};
+    }
+  }
+  *(f32x4*)(col + row * Kp + k0) = o;
+}
+
+// encoder prologue, fp32: one thread = 4 consecutive columns (ky, kx, c) of one output row (vae_enc_prologue_kernel's values,
+// not rounded)
+__global__ __launch_bounds__(256) void vae_enc_prologue_f32_kernel(const void* __restrict__ img, int u8, int flip, float* __restrict__ col,
+                                                                   int B, int R, int Kp) {
+  const int chunks = Kp >> 2;
+  const long total = (long)B * R * R * chunks;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int ch = (int)(idx % chunks);
+  const long row = idx / chunks;
+  const int xo = (int)(row % R), yo = (int)((row / R) % R), b = (int)(row / ((long)R * R));
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int k = ch * 4 + e, tap = k / 3, c = k - tap * 3;
+    const int yy = yo + tap / 3 - 1, xx = xo + tap % 3 - 1;
+    float v = 0.f;
+    if (k < 27 && yy >= 0 && yy < R && xx >= 0 && xx < R) {
+      const int sx = flip ? R - 1 - xx : xx;
+      if (u8) {
+        const float u = (float)((const unsigned char*)img)[(((long)b * R + yy) * R + sx) * 3 + c];
+        v = __fdiv_rn(__fdiv_rn(u, 255.f) - 0.5f, 0.5f);
+      } else {
+        v = ((const float*)img)[(((long)b * 3 + c) * R + yy) * R + sx];
+      }
+    }
+    o[e] = v;
+  }
+  *(f32x4*)(col + row * Kp + ch * 4) = o;
+}
+
+// ------------------------------------------------------------------------------------------
+
+extern "C" long mdt_gn_stats_ordered_ws_floats(int B, int groups) { return (4096L + B) * groups * 2; }
+
+extern "C" int mdt_gn_stats_ordered(const float* x, float* sums, float* ws, int B, int HW, int C, int groups, mdt_stream_t stream) {
+  MDT_REQUIRE(x && sums && ws, "gn_stats_ordered: null pointer");
+  MDT_REQUIRE(B > 0 && B <= 65535 && HW > 0 && C % 4 == 0 && C > 0 && C <= 1024 && 1024 % C == 0 && groups > 0 && groups <= 256 &&
+                  C % groups == 0 && (C / groups) % 4 == 0,
+              "gn_stats_ordered: C must divide 1024 with C / groups a multiple of 4, B <= 65535");
+  int chunks = 1;  // (B * chunks < 4096: the partials fit mdt_gn_stats_ordered_ws_floats)
+  while ((long)B * chunks < 2048 && HW / (chunks * 2) >= 64) chunks *= 2;
+  const int ppb = cdiv(HW, chunks);
+  const int nch = cdiv(HW, ppb);
+  hipLaunchKernelGGL(gn_stats_part_kernel, dim3(nch, B), dim3(256), 0, (hipStream_t)stream, x, ws, HW, C, groups, ppb);
+  hipLaunchKernelGGL(gn_stats_fold_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const float*)ws, sums, nch, groups);
+  return mdt_check_launch("gn_stats_ordered");
+}
+
+extern "C" int mdt_gn_im2col_f32(const float* x, const float* sums, const float* gamma, const float* beta, float* col, int B,
+                                 int H, int W, int C, int groups, int ksize, int upsample, int swish, int Kp, mdt_stream_t stream) {
+  MDT_REQUIRE(x && col, "gn_im2col_f32: null pointer");
+  MDT_REQUIRE(!sums || (gamma && beta && groups > 0 && C % groups == 0), "gn_im2col_f32: normalisation needs sums, gamma, beta, groups");
+  MDT_REQUIRE((ksize == 1 || ksize == 3) && (upsample == 0 || upsample == 1), "gn_im2col_f32: 1x1 / 3x3 taps, optional 2x up-sampling");
+  MDT_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && Kp % 4 == 0 && Kp >= ksize * ksize * C,
+              "gn_im2col_f32: C % 4, Kp % 4, Kp >= k*k*C");
+  MDT_REQUIRE((((uintptr_t)x | (uintptr_t)col) & 15) == 0 && (!sums || (((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0),
+              "gn_im2col_f32: x, col, gamma, beta must be 16-byte aligned");
+  const long total = (long)B * (H << upsample) * (W << upsample) * (Kp / 4);
+  MDT_REQUIRE(total > 0 && total / 256 < 2147483647L, "gn_im2col_f32: problem size");
+  const float inv_n = sums ? 1.f / ((float)H * (float)W * (float)(C / groups)) : 0.f;
+  hipLaunchKernelGGL(gn_im2col_f32_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, sums, gamma, beta,
+                     col, B, H, W, C, groups > 0 ? groups : 1, ksize, upsample, swish, Kp, inv_n);
+  return mdt_check_launch("gn_im2col_f32");
+}
+
+extern "C" int mdt_vae_enc_prologue_f32(const void* img, int u8, int flip, float* col, int B, int R, int Kp, mdt_stream_t stream) {
+  MDT_REQUIRE(img && col, "vae_enc_prologue_f32: null pointer");
+  MDT_REQUIRE((u8 == 0 || u8 == 1) && (flip == 0 || flip == 1), "vae_enc_prologue_f32: u8 and flip are 0 or 1");
+  MDT_REQUIRE(B > 0 && R > 0 && Kp >= 27 && Kp % 4 == 0 && ((uintptr_t)col & 15) == 0,
+              "vae_enc_prologue_f32: B, R > 0, Kp >= 27 and a multiple of 4, col 16-byte aligned");
+  const long total = (long)B * R * R * (Kp / 4);
+  MDT_REQUIRE(total / 256 < 2147483647L, "vae_enc_prologue_f32: problem size");
+  hipLaunchKernelGGL(vae_enc_prologue_f32_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, img, u8, flip,
+                     col, B, R, Kp);
+  return mdt_check_launch("vae_enc_prologue_f32");
+}
 
 extern "C" int mdt_gn_stats(const float* x, float* sums, int B, int HW, int C, int groups, mdt_stream_t stream) {
   MDT_REQUIRE(x && sums, "gn_stats: null pointer");
