@@ -348,6 +348,58 @@ int mdt_silu_f32(const float* in, float* out, long n, mdt_stream_t stream);
 /* out[(b, j), :] = in[(b, j), :] + rows[j, :], j = row % T: `x + decoder_pos_embed` (models/maskdit.py:545); D % 4 == 0 */
 int mdt_add_rows_f32(const float* in, const float* rows, float* out, long n_rows, int T, int D, mdt_stream_t stream);
 
+/* ---------------------------------------------------------------- fp32 training (unmasked stage) ---- */
+
+/* The reference's second stage, "finetune with unmasking" (README.md:102-119, configs/finetune: mask_ratio 0), is launched
+ * with --no_amp (train.py:39-46): fp32 forward AND backward.  The entries below, with the exact-fp32 forward entries above,
+ * are that backward (csrc/f32train.hip).  All of them are deterministic: no atomics, split reductions are folded in index
+ * order, repeated calls give identical bits.  Data gradients dX = dY W use mdt_gemm_f32 with b_kmajor = 1 (W [N, K] read
+ * as the K-major operand). */
+/* C[z][N1,N2] (+)= A[z][M,N1]^T * B[z][M,N2]: the weight gradient of every nn.Linear (A = output gradient, B = layer input,
+ * the reduction runs over the M tokens) and, batched over z = b * heads + h with operand bases base + b * stride_b +
+ * h * stride_h (elements), attention's dk = dS^T q and dv = P^T dO on the packed qkv buffer.  accumulate != 0: C += (the
+ * gradient arena's autograd semantics).  M is cut into fixed chunks (a function of M, N1, N2, batch only); with more than
+ * one chunk the per-chunk products go to `ws` (mdt_gemm_f32_tn_ws_floats() floats, 16-byte aligned; 0 = not needed, ws may be
+ * NULL) and are added in chunk order.  N1, N2 multiples of 4, 16-byte aligned operand rows / strides; M arbitrary. */
+typedef struct {
+  const float* A; long lda;
+  const float* B; long ldb;
+  int M, N1, N2;
+  float* C; long ldc;
+  int accumulate;
+  int batch, heads; /* 0 = 1 */
+  long a_stride_b, a_stride_h, b_stride_b, b_stride_h, c_stride_b, c_stride_h;
+  float* ws; long ws_floats;
+} mdt_gemm_f32_tn_args;
+long mdt_gemm_f32_tn_ws_floats(int M, int N1, int N2, int batch);
+int mdt_gemm_f32_tn(const mdt_gemm_f32_tn_args* a, mdt_stream_t stream);
+/* out[n] (+)= sum_m in[m, n]: bias gradients.  Rows are summed in chunks whose partial sums go to `ws`
+ * (mdt_colsum_f32_ws_floats() floats; 0 = not needed) and are added in chunk order.  N % 4 == 0. */
+long mdt_colsum_f32_ws_floats(int M, int N);
+int mdt_colsum_f32(const float* in, long ld, float* out, float* ws, long ws_floats, int M, int N, int accumulate,
+                   mdt_stream_t stream);
+/* backward of mdt_attn_f32: dqkv [B*L, 3*H*hd] from dout [B*L, H*hd]; every element of dqkv is written.  P is recomputed;
+ * `ws` holds mdt_attn_f32_bwd_ws_floats() floats (two score matrices per (sample, head) + the transposed products' own
+ * workspace).  L and hd multiples of 4, B * H <= 65535. */
+long mdt_attn_f32_bwd_ws_floats(int B, int L, int H, int hd);
+int mdt_attn_f32_bwd(const float* qkv, const float* dout, float* ws, long ws_floats, float* dqkv, int B, int L, int H, int hd,
+                     mdt_stream_t stream);
+/* backward of mdt_ln_modulate_f32: dx (+)= dLN(dxn * (1 + scale)); dshift[b] = sum_l dxn; dscale[b] = sum_l dxn * xhat (both
+ * STORED, the sample's rows added in a fixed order).  The row statistics are recomputed from x; stats_ws = 2 * M floats. */
+int mdt_ln_modulate_bwd_f32(const float* dxn, const float* x, const float* scale, int mod_ld, int rows_per_sample, float* dx,
+                            int accumulate, float* dshift, float* dscale, int dmod_ld, float* stats_ws, int M, int D,
+                            mdt_stream_t stream);
+/* backward of `x + gate * f` (models/maskdit.py:190-191): df = gate[b] * dy; dgate[b] = sum_l dy * f (stored, fixed order) */
+int mdt_gate_bwd_f32(const float* dy, const float* f, const float* gate, int gate_ld, int rows_per_sample, float* df,
+                     float* dgate, int dgate_ld, int M, int D, mdt_stream_t stream);
+/* out = res + gate[row / rows_per_sample] * f: the residual add of the training forward, which keeps f for the backward */
+int mdt_gate_res_f32(const float* res, const float* f, const float* gate, int gate_ld, int rows_per_sample, float* out, int M,
+                     int D, mdt_stream_t stream);
+/* out = gelu_tanh(in) (timm Mlp act, models/maskdit.py:181); dx = dy * gelu_tanh'(x); dx = dy * silu'(x) */
+int mdt_gelu_f32(const float* in, float* out, long n, mdt_stream_t stream);
+int mdt_gelu_bwd_f32(const float* dy, const float* x, float* dx, long n, mdt_stream_t stream);
+int mdt_silu_bwd_f32(const float* dy, const float* x, float* dx, long n, mdt_stream_t stream);
+
 /* ---------------------------------------------------------------- VAE decoder glue ------ */
 
 /* The KL-autoencoder decoder that follows the sampler (autoencoder.py:306-410 Decoder, :449-453 decode; call sites

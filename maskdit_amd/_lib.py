@@ -46,6 +46,14 @@ class GemmF32Args(C.Structure):
 
 F32EPI_NONE, F32EPI_GELU, F32EPI_SILU, F32EPI_GATE_RES = range(4)
 
+
+class GemmF32TNArgs(C.Structure):
+    _fields_ = [('A', vp), ('lda', i64), ('B', vp), ('ldb', i64), ('M', i32), ('N1', i32), ('N2', i32), ('C', vp), ('ldc', i64),
+                ('accumulate', i32), ('batch', i32), ('heads', i32),
+                ('a_stride_b', i64), ('a_stride_h', i64), ('b_stride_b', i64), ('b_stride_h', i64),
+                ('c_stride_b', i64), ('c_stride_h', i64), ('ws', vp), ('ws_floats', i64)]
+
+
 # name -> argtypes (the trailing stream argument is added to every compute entry)
 _PROTOS = {
     'mdt_gemm_nt': [C.POINTER(GemmNTArgs)],
@@ -110,6 +118,15 @@ _PROTOS = {
     'mdt_timestep_embed_f32': [vp, vp, i32, i32, i32],
     'mdt_silu_f32': [vp, vp, i64],
     'mdt_add_rows_f32': [vp, vp, vp, i64, i32, i32],
+    'mdt_gemm_f32_tn': [C.POINTER(GemmF32TNArgs)],
+    'mdt_colsum_f32': [vp, i64, vp, vp, i64, i32, i32, i32],
+    'mdt_attn_f32_bwd': [vp, vp, vp, i64, vp, i32, i32, i32, i32],
+    'mdt_ln_modulate_bwd_f32': [vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, vp, i32, i32],
+    'mdt_gate_bwd_f32': [vp, vp, vp, i32, i32, vp, vp, i32, i32, i32],
+    'mdt_gate_res_f32': [vp, vp, vp, i32, i32, vp, i32, i32],
+    'mdt_gelu_f32': [vp, vp, i64],
+    'mdt_gelu_bwd_f32': [vp, vp, vp, i64],
+    'mdt_silu_bwd_f32': [vp, vp, vp, i64],
 }
 # entries without the trailing stream
 _PLAIN = {
@@ -126,6 +143,9 @@ _PLAIN = {
     'mdt_nt8o_stamps': [C.POINTER(C.c_uint64)],
     'mdt_attn_f32_ws_floats': [i32, i32, i32, i32],
     'mdt_gn_stats_ordered_ws_floats': [i32, i32],
+    'mdt_gemm_f32_tn_ws_floats': [i32, i32, i32, i32],
+    'mdt_colsum_f32_ws_floats': [i32, i32],
+    'mdt_attn_f32_bwd_ws_floats': [i32, i32, i32, i32],
 }
 EXPORTED = sorted(list(_PROTOS) + list(_PLAIN) + ['mdt_last_error', 'mdt_version'])
 ABI_VERSION = 4  # == MDT_ABI_VERSION of include/maskdit_hip.h (tests/test_capi_cpu.py compares the two)

@@ -31,7 +31,7 @@ import torch
 
 from . import _lib
 from ._lib import (EPI_BF16, EPI_DGELU, EPI_DSILU, EPI_F32, EPI_GATE_RES, EPI_GELU, EPI_SILU, F32EPI_GATE_RES,
-                   F32EPI_GELU, F32EPI_NONE, F32EPI_SILU, GemmF32Args, GemmNTArgs, GemmTNArgs)
+                   F32EPI_GELU, F32EPI_NONE, F32EPI_SILU, GemmF32Args, GemmF32TNArgs, GemmNTArgs, GemmTNArgs)
 
 DEC_HIDDEN, DEC_DEPTH, DEC_HEADS = 512, 8, 16  # models/maskdit.py:310-312
 MODEL_CONFIGS = {  # models/maskdit.py:649-715  name -> (depth, hidden, patch, heads)
@@ -318,9 +318,11 @@ class Engine:
         (PassPlan.set_valid)."""
         global _PLAN_CLOCK
         check_precision(precision)
-        if reads_f32_arena(precision) and (masked or train):
-            raise NotImplementedError('the fp32-faithful path covers inference (the sampler / eval forward: sample.py:56); '
-                                      'fp32 TRAINING (train.py --no_amp) is not provided')
+        f32_train = precision == 'fp32' and train and not masked  # the unmasked stage (train.py --no_amp): _build_f32_train
+        if reads_f32_arena(precision) and (masked or train) and not f32_train:
+            raise NotImplementedError('the fp32-faithful path covers inference (the sampler / eval forward: sample.py:56) and, at '
+                                      "precision 'fp32', training of the UNMASKED stage (mask_ratio 0: train.py --no_amp); fp32 "
+                                      "TRAINING of the masked stage and a 'bf16x3' training plan are not provided")
         Lv = (L if L is not None else self.sp.T // 2) if masked else None
         key = plan_key(B, masked, train, Lv, precision)
         pl = self._plans.pop(key, None)
@@ -334,7 +336,8 @@ class Engine:
             # until it fits (5 % of the device stays free for the caller's own tensors) or nothing is left to drop.
             while len(self._plans) >= 8:
                 _drop_plan(self, next(iter(self._plans)))
-            need = PassPlan.estimate_bytes(self.sp, B, masked, train, Lv) * (2 if reads_f32_arena(precision) else 1)
+            need = PassPlan.estimate_bytes_f32_train(self.sp, B) if f32_train else \
+                PassPlan.estimate_bytes(self.sp, B, masked, train, Lv) * (2 if reads_f32_arena(precision) else 1)
             # (a plan something else still refers to -- a pending backward, a captured sampler graph -- gives no memory back
             # when its cache entry goes: after two evictions in a row that freed nothing the loop stops instead of emptying
             # every engine's cache for no gain)
@@ -344,6 +347,13 @@ class Engine:
                 if not _evict_lru_plan(self.device):
                     break
                 fruitless = fruitless + 1 if _device_available(self.device) <= before else 0
+            if f32_train and need > _device_available(self.device):
+                # the estimate of this plan is exact to a few per cent (estimate_bytes_f32_train), so a batch that cannot fit
+                # is refused here, with the figures, instead of somewhere inside the allocator
+                raise RuntimeError(f'maskdit_amd: an fp32 training plan for batch {B} needs {need / 2**30:.1f} GiB of activations and '
+                                   f'workspace ({need / B / 2**20:.0f} MiB per sample), the device has '
+                                   f'{_device_available(self.device) / 2**30:.1f} GiB available after dropping every cached plan: '
+                                   'use a smaller micro-batch (train.batchsize) with train.grad_accum')
             while True:
                 try:
                     pl = PassPlan(self, B, masked, train, Lv, precision)
@@ -477,7 +487,9 @@ class PassPlan:
         self.fwd = Plan()
         self.bwd = Plan()
         self.gen = 0  # forward generation: the saved activations belong to the LAST forward through this plan
-        if reads_f32_arena(precision):
+        if reads_f32_arena(precision) and train:
+            self._build_f32_train()
+        elif reads_f32_arena(precision):
             self._build_f32()
         else:
             self._build()
@@ -774,8 +786,268 @@ class PassPlan:
               Pf('model.final_layer.linear.weight'), Pf('model.final_layer.linear.bias'), Fx.data_ptr(), st_f.data_ptr(),
               B, T, Dd, sp.C, sp.patch)
 
+    # ---- fp32 training of the unmasked stage (csrc/f32train.hip) -----------------------------------------------------
+    @staticmethod
+    def _ada_kchunk(NM: int) -> int:
+        """Chunk of the stacked adaLN data-gradient contraction: the largest divisor of NM that is a multiple of 4 and <= 1024."""
+        return next(c for c in range(1024, 3, -4) if NM % c == 0)
+
+    @staticmethod
+    def _f32_train_ws(sp, B: int) -> Tuple[int, int, int]:
+        """Floats of the three library workspaces of an fp32 training plan: transposed products, column sums, attention
+        backward -- each the largest request among the plan's launches (queried from the library)."""
+        L = _lib.lib()
+        M, NM, D, Dd = B * sp.T, sp.n_mod, sp.D, sp.Dd
+        tn_shapes = [(B, NM, D), (B, D, sp.num_classes), (B, D, D), (B, D, 256), (M, Dd, D)]
+        for W in (D, Dd):
+            tn_shapes += [(M, W, 4 * W), (M, 4 * W, W), (M, W, W), (M, 3 * W, W)]
+        tn = max(int(L.mdt_gemm_f32_tn_ws_floats(m, n1, n2, 1)) for m, n1, n2 in tn_shapes)
+        cs = max(int(L.mdt_colsum_f32_ws_floats(M, 4 * max(D, Dd))), int(L.mdt_colsum_f32_ws_floats(B, NM)),
+                 int(L.mdt_colsum_f32_ws_floats(NM // PassPlan._ada_kchunk(NM), B * D)))
+        at = max(int(L.mdt_attn_f32_bwd_ws_floats(B, sp.T, sp.heads, sp.hd)), int(L.mdt_attn_f32_bwd_ws_floats(B, sp.T, sp.dheads, sp.dhd)))
+        return tn, cs, at
+
+    @staticmethod
+    def f32_train_floats(sp, B: int) -> Dict[str, int]:
+        """fp32 elements of an fp32 training plan's buffers by group: the figures _build_f32_train allocates."""
+        M, W = B * sp.T, max(sp.D, sp.Dd)
+        tn, cs, at = PassPlan._f32_train_ws(sp, B)
+        saved = 12 * M * (sp.depth * sp.D + sp.ddepth * sp.Dd)  # per block: x_out, qkv (3), ao, f_attn, x_mid, h (4), f_mlp
+        stream = M * (sp.D + 2 * sp.Dd) + 2 * M + M * (sp.D + sp.Dd)  # x_e0, x_d0, xdec, final-layer stats, dx_e, dx_d
+        shared = 5 * M * (sp.D + sp.Dd)                         # xn + act (4) per stack
+        work = 10 * M * W + 2 * M                               # df, dh (4), dxn, dao, dqkv (3), LayerNorm statistics
+        cond = B * (2 * sp.n_mod + (9 + sp.n_mod // PassPlan._ada_kchunk(sp.n_mod)) * sp.D + 256 + sp.num_classes + 8) + 6 * B * sp.C * sp.R * sp.R
+        return dict(saved=saved, stream=stream, shared=shared, work=work, attn=at, wgrad=tn + cs, cond=cond)
+
+    @staticmethod
+    def estimate_bytes_f32_train(sp, B: int) -> int:
+        return int(4 * sum(PassPlan.f32_train_floats(sp, B).values()) * 1.02)
+
+    def _build_f32_train(self):
+        """Forward + backward of the UNMASKED training step in exact fp32: the reference's second stage ("finetune with
+        unmasking", README.md:102-119: mask_ratio 0, train.py --no_amp).  The forward is _build_f32's graph with per-block
+        saved activations (and unfused GELU / gate + residual passes, so that the pre-activation h and the branch outputs
+        f survive); the backward is the hand-derived gradient of the same graph, filling the gradient arena the bf16 plan
+        fills with the same `+=` semantics.  Weights are read from the fp32 master arena: no bf16 shadow is involved.
+        LayerNorm outputs and GELU outputs are recomputed in the backward instead of being kept (12 instead of 18 floats
+        per token, block and channel)."""
+        eng, sp, lay = self.eng, self.eng.sp, self.eng.lay
+        B, T, D, Dd = self.B, self.T, sp.D, sp.Dd
+        NM = sp.n_mod
+        if self.masked or self.precision != 'fp32':
+            raise NotImplementedError("fp32 training covers the unmasked stage at precision 'fp32' only")
+        if sp.num_classes % 4:
+            raise NotImplementedError('fp32 path: num_classes must be a multiple of 4 (16-byte label rows)')
+        if B * max(sp.heads, sp.dheads) > 65535:
+            raise NotImplementedError('fp32 path: batch * heads must not exceed 65535 (one grid row per (sample, head))')
+        Pp = eng.P.data_ptr()
+        Gp = eng.ensure_grad().data_ptr()
+
+        def Pf(name):
+            return Pp + 4 * lay.off[name]
+
+        def Gf(name):
+            return Gp + 4 * lay.off[name]
+
+        f, g = self.fwd, self.bwd
+        M = B * T
+        xin = self.f32('xin', B, sp.C, sp.R, sp.R)
+        coef = self.f32('coef', 8, B)
+        cn = coef[3]
+        self.buf['c_noise'] = cn
+        lab = self.f32('labels', B, sp.num_classes)
+        Fx = self.f32('F', B, sp.C, sp.R, sp.R)
+        dF = self.f32('dF', B, sp.C, sp.R, sp.R)
+        for nm in ('yn', 'D', 'y'):  # EDMLoss's own buffers, as in _build
+            self.f32(nm, B, sp.C, sp.R, sp.R)
+        # ---- workspaces shared by the whole backward: sized for the largest request ------------------------------------
+        Wm = max(D, Dd)
+        tn_floats, cs_floats, at_floats = self._f32_train_ws(sp, B)
+        tnws = self.f32('ws_tn', max(tn_floats, 4))
+        csws = self.f32('ws_colsum', max(cs_floats, 4))
+        atws = self.f32('ws_attn', at_floats)
+        self._f32ws = dict(tn=(tnws.data_ptr(), tn_floats), cs=(csws.data_ptr(), cs_floats), at=(atws.data_ptr(), at_floats),
+                           df=self.f32('ws_df', M * Wm), dh=self.f32('ws_dh', 4 * M * Wm), dxn=self.f32('ws_dxn', M * Wm),
+                           dao=self.f32('ws_dao', M * Wm), dqkv=self.f32('ws_dqkv', 3 * M * Wm), stats=self.f32('ws_stats', 2 * M))
+        # ---------------- conditioning path -----------------------------------------------------------------------------
+        temb, h1, a1 = self.f32('temb', B, 256), self.f32('h1', B, D), self.f32('a1', B, D)
+        c_t, c, sc = self.f32('c_t', B, D), self.f32('c', B, D), self.f32('sc', B, D)
+        mod = self.f32('mod', B, NM)
+        f.add('mdt_timestep_embed_f32', cn.data_ptr(), temb.data_ptr(), 256, B, 256)
+        self._g32(temb, 256, Pf('model.t_embedder.mlp.0.weight'), 256, B, D, 256, h1, D, bias=Pf('model.t_embedder.mlp.0.bias'))
+        f.add('mdt_silu_f32', h1.data_ptr(), a1.data_ptr(), B * D)
+        self._g32(a1, D, Pf('model.t_embedder.mlp.2.weight'), D, B, D, D, c_t, D, bias=Pf('model.t_embedder.mlp.2.bias'))
+        self._g32(lab, sp.num_classes, Pf('model.y_embedder.embedding_table.weight'), sp.num_classes, B, D, sp.num_classes, c, D,
+                  epi=F32EPI_GATE_RES, res=c_t, ldres=D, rps=1)
+        f.add('mdt_silu_f32', c.data_ptr(), sc.data_ptr(), B * D)
+        self._g32(sc, D, Pp + 4 * lay.ada_w, D, B, NM, D, mod, NM, bias=Pp + 4 * lay.ada_b)
+        # ---------------- encoder -----------------------------------------------------------------------------------------
+        x = self.f32('x_e0', M, D)
+        f.add('mdt_patch_embed_fwd', xin.data_ptr(), None, Pf('model.x_embedder.proj.weight'), Pf('model.x_embedder.proj.bias'),
+              eng.pos.data_ptr(), None, 2 * T, x.data_ptr(), B, sp.C, sp.R, sp.patch, T, D)
+        xs_e = [x]
+        for i in range(sp.depth):
+            xs_e.append(self._block_fwd_f32t(f'model.blocks.{i}', 'e', i, xs_e[-1], mod, sp.mod_off('enc', i), D, sp.heads, T, M))
+        self.marks = {'enc_fwd_end': len(f.calls)}
+        odl = sp.mod_off('dl')
+        xn_e, xdec = self.f32('xn_e', M, D), self.f32('xdec', M, Dd)
+        f.add('mdt_ln_modulate_f32', xs_e[-1].data_ptr(), mod.data_ptr() + 4 * odl, mod.data_ptr() + 4 * (odl + D), NM, T,
+              xn_e.data_ptr(), M, D)
+        self._g32(xn_e, D, Pf('model.decoder_layer.linear.weight'), D, M, Dd, D, xdec, Dd, bias=Pf('model.decoder_layer.linear.bias'))
+        xd0 = self.f32('x_d0', M, Dd)
+        f.add('mdt_add_rows_f32', xdec.data_ptr(), eng.dpos.data_ptr(), xd0.data_ptr(), M, T, Dd)
+        xs_d = [xd0]
+        for i in range(sp.ddepth):
+            xs_d.append(self._block_fwd_f32t(f'model.decoder_blocks.{i}', 'd', i, xs_d[-1], mod, sp.mod_off('dec', i), Dd, sp.dheads, T, M))
+        ofin = sp.mod_off('fin')
+        st_f = self.f32('st_f', M, 2)
+        f.add('mdt_final_fwd', xs_d[-1].data_ptr(), mod.data_ptr() + 4 * ofin, mod.data_ptr() + 4 * (ofin + Dd), NM,
+              Pf('model.final_layer.linear.weight'), Pf('model.final_layer.linear.bias'), Fx.data_ptr(), st_f.data_ptr(),
+              B, T, Dd, sp.C, sp.patch)
+        # =================== backward =====================================================================================
+        dmod = self.f32('dmod', B, NM)
+        dxe, dxd = self.f32('dx_e', M, D), self.f32('dx_d', M, Dd)
+        ws = self._f32ws
+        g.add_callback(lambda: dmod.zero_())  # (mdt_final_bwd adds its two modulation gradients; every other column is stored)
+        g.add('mdt_final_bwd', dF.data_ptr(), xs_d[-1].data_ptr(), st_f.data_ptr(), mod.data_ptr() + 4 * ofin,
+              mod.data_ptr() + 4 * (ofin + Dd), NM, Pf('model.final_layer.linear.weight'), dxd.data_ptr(),
+              Gf('model.final_layer.linear.weight'), Gf('model.final_layer.linear.bias'), dmod.data_ptr() + 4 * ofin,
+              dmod.data_ptr() + 4 * (ofin + Dd), NM, B, T, Dd, sp.C, sp.patch)
+        for i in reversed(range(sp.ddepth)):
+            self._block_bwd_f32(f'model.decoder_blocks.{i}', 'd', i, xs_d[i], mod, dmod, sp.mod_off('dec', i), Dd, sp.dheads, T, M, dxd, Gf)
+            self._slab(f'dec{i}')
+        # x_d0 = xdec + decoder_pos_embed: d xdec = dx_d.  mask_token takes no part in an unmasked pass: its gradient stays
+        # the zero _prepare_grad_arena wrote (train_utils/loss.py:57-58 adds 0 * mask_token.sum() for the same effect)
+        f32 = F32EPI_NONE
+        g.add('mdt_ln_modulate_f32', xs_e[-1].data_ptr(), mod.data_ptr() + 4 * odl, mod.data_ptr() + 4 * (odl + D), NM, T,
+              xn_e.data_ptr(), M, D)
+        self._tn32(dxd, Dd, xn_e, D, M, Dd, D, Gf('model.decoder_layer.linear.weight'), D)
+        self._cs32(dxd, Dd, Gf('model.decoder_layer.linear.bias'), M, Dd)
+        self._g32(dxd, Dd, Pf('model.decoder_layer.linear.weight'), D, M, D, Dd, ws['dxn'], D, epi=f32, b_kmajor=1, to=g)
+        g.add('mdt_ln_modulate_bwd_f32', ws['dxn'].data_ptr(), xs_e[-1].data_ptr(), mod.data_ptr() + 4 * (odl + D), NM, T,
+              dxe.data_ptr(), 0, dmod.data_ptr() + 4 * odl, dmod.data_ptr() + 4 * (odl + D), NM, ws['stats'].data_ptr(), M, D)
+        self.marks['enc_bwd_begin'] = len(g.calls)
+        for i in reversed(range(sp.depth)):
+            self._block_bwd_f32(f'model.blocks.{i}', 'e', i, xs_e[i], mod, dmod, sp.mod_off('enc', i), D, sp.heads, T, M, dxe, Gf)
+            self._slab(f'enc{i}')
+        g.add('mdt_patch_embed_bwd', xin.data_ptr(), None, dxe.data_ptr(), None, 2 * T, Gf('model.x_embedder.proj.weight'),
+              Gf('model.x_embedder.proj.bias'), B, sp.C, sp.R, sp.patch, T, D)
+        # ---- every modulation gradient is final: the stacked adaLN Linear (one weight-gradient product), then the
+        # conditioning path (SiLU, label table, timestep MLP) ------------------------------------------------------------
+        self._tn32(dmod, NM, sc, D, B, NM, D, Gp + 4 * lay.ada_w, D)
+        self._cs32(dmod, NM, Gp + 4 * lay.ada_b, B, NM)
+        for name, _, _ in lay.ada_groups:
+            self._slab(name)
+        self._slab('ada_b')
+        dsc, dc, da1 = self.f32('dsc', B, D), self.f32('dc', B, D), self.f32('da1', B, D)
+        # d silu(c) = dmod W_ada contracts over EVERY modulation output (54 k on S/2, 221 k on XL/2): one fp32 accumulator chain
+        # of that length loses ~ sqrt(K) ulp against a blocked sum, so the contraction is cut into equal chunks (one batched
+        # launch, one partial [B, D] per chunk) that mdt_colsum_f32 adds in chunk order
+        ck = self._ada_kchunk(NM)
+        nch = NM // ck
+        dsc_part = self.f32('dsc_part', nch, B, D)
+        self._g32(dmod, NM, Pp + 4 * lay.ada_w, D, B, D, ck, dsc_part, D, epi=f32, b_kmajor=1, batch=nch, heads=1, a_s=(ck, 0),
+                  b_s=(ck * D, 0), o_s=(B * D, 0), to=g)
+        g.add('mdt_colsum_f32', dsc_part.data_ptr(), B * D, dsc.data_ptr(), ws['cs'][0], ws['cs'][1], nch, B * D, 0)
+        g.add('mdt_silu_bwd_f32', dsc.data_ptr(), c.data_ptr(), dc.data_ptr(), B * D)
+        self._tn32(dc, D, lab, sp.num_classes, B, D, sp.num_classes, Gf('model.y_embedder.embedding_table.weight'), sp.num_classes)
+        self._tn32(dc, D, a1, D, B, D, D, Gf('model.t_embedder.mlp.2.weight'), D)
+        self._cs32(dc, D, Gf('model.t_embedder.mlp.2.bias'), B, D)
+        self._g32(dc, D, Pf('model.t_embedder.mlp.2.weight'), D, B, D, D, da1, D, epi=f32, b_kmajor=1, to=g)
+        g.add('mdt_silu_bwd_f32', da1.data_ptr(), h1.data_ptr(), da1.data_ptr(), B * D)
+        self._tn32(da1, D, temb, 256, B, D, 256, Gf('model.t_embedder.mlp.0.weight'), 256)
+        self._cs32(da1, D, Gf('model.t_embedder.mlp.0.bias'), B, D)
+        self._slab('misc')
+
+    def _tn32(self, A, lda, Bm, ldb, M, N1, N2, Cp, ldc):
+        """One mdt_gemm_f32_tn launch of the backward plan: C += A^T B into the gradient arena (address Cp)."""
+        a = GemmF32TNArgs()
+        a.A, a.lda, a.B, a.ldb = A.data_ptr(), lda, Bm.data_ptr(), ldb
+        a.M, a.N1, a.N2 = M, N1, N2
+        a.C, a.ldc, a.accumulate = Cp, ldc, 1
+        a.ws, a.ws_floats = self._f32ws['tn']
+        self.bwd.add('mdt_gemm_f32_tn', C.byref(self._k(a)))
+
+    def _cs32(self, A, ld, outp, M, N):
+        """bias gradient: out += column sums of A"""
+        wsp, wsn = self._f32ws['cs']
+        self.bwd.add('mdt_colsum_f32', A.data_ptr(), ld, outp, wsp, wsn, M, N, 1)
+
+    def _block_fwd_f32t(self, prefix, tag, i, x_in, mod, moff, W, heads, rows, M):
+        """DiTBlock.forward (models/maskdit.py:188-192) in fp32, keeping what the backward needs: qkv, the attention output,
+        both branch outputs f (so the residual adds are passes of their own), x_mid and the pre-GELU h."""
+        eng, lay, f = self.eng, self.eng.lay, self.fwd
+        NM = eng.sp.n_mod
+        hd = W // heads
+        B = self.B
+        s = f'{tag}{i}'
+        Pp = eng.P.data_ptr()
+        Pf = lambda n: Pp + 4 * lay.off[f'{prefix}.{n}']  # noqa: E731
+        mp = mod.data_ptr()
+        sh1, sc1, g1, sh2, sc2, g2 = (mp + 4 * (moff + k * W) for k in range(6))
+        xn, act = self.f32(f'xn_{tag}', M, W), self.f32(f'act_{tag}', M, 4 * W)  # shared: recomputed by the backward
+        qkv, ao, fa = self.f32(f'qkv_{s}', M, 3 * W), self.f32(f'ao_{s}', M, W), self.f32(f'fa_{s}', M, W)
+        xmid, h, fm = self.f32(f'xmid_{s}', M, W), self.f32(f'h_{s}', M, 4 * W), self.f32(f'fm_{s}', M, W)
+        xout = self.f32(f'x_{tag}{i + 1}', M, W)
+        ws_floats = int(_lib.lib().mdt_attn_f32_ws_floats(B, rows, heads, hd))
+        S = self._f32ws['at'][0] if ws_floats else None  # (the backward's score workspace is at least twice as large)
+        f.add('mdt_ln_modulate_f32', x_in.data_ptr(), sh1, sc1, NM, rows, xn.data_ptr(), M, W)
+        self._g32(xn, W, Pf('attn.qkv.weight'), W, M, 3 * W, W, qkv, 3 * W, bias=Pf('attn.qkv.bias'))
+        f.add('mdt_attn_f32', qkv.data_ptr(), ao.data_ptr(), S, B, rows, heads, hd)
+        self._g32(ao, W, Pf('attn.proj.weight'), W, M, W, W, fa, W, bias=Pf('attn.proj.bias'))
+        f.add('mdt_gate_res_f32', x_in.data_ptr(), fa.data_ptr(), g1, NM, rows, xmid.data_ptr(), M, W)
+        f.add('mdt_ln_modulate_f32', xmid.data_ptr(), sh2, sc2, NM, rows, xn.data_ptr(), M, W)
+        self._g32(xn, W, Pf('mlp.fc1.weight'), W, M, 4 * W, W, h, 4 * W, bias=Pf('mlp.fc1.bias'))
+        f.add('mdt_gelu_f32', h.data_ptr(), act.data_ptr(), M * 4 * W)
+        self._g32(act, 4 * W, Pf('mlp.fc2.weight'), 4 * W, M, W, 4 * W, fm, W, bias=Pf('mlp.fc2.bias'))
+        f.add('mdt_gate_res_f32', xmid.data_ptr(), fm.data_ptr(), g2, NM, rows, xout.data_ptr(), M, W)
+        return xout
+
+    def _block_bwd_f32(self, prefix, tag, i, x_in, mod, dmod, moff, W, heads, rows, M, dx, Gf):
+        """Backward of DiTBlock in fp32: dx (the residual-stream gradient) is updated in place."""
+        eng, lay, g, ws = self.eng, self.eng.lay, self.bwd, self._f32ws
+        NM = eng.sp.n_mod
+        hd = W // heads
+        B = self.B
+        s = f'{tag}{i}'
+        Pp = eng.P.data_ptr()
+        Pf = lambda n: Pp + 4 * lay.off[f'{prefix}.{n}']  # noqa: E731
+        Gn = lambda n: Gf(f'{prefix}.{n}')  # noqa: E731
+        mp, dp = mod.data_ptr(), dmod.data_ptr()
+        sh1, sc1, g1, sh2, sc2, g2 = (mp + 4 * (moff + k * W) for k in range(6))
+        dsh1, dsc1, dg1, dsh2, dsc2, dg2 = (dp + 4 * (moff + k * W) for k in range(6))
+        b = self.buf
+        xn, act = b[f'xn_{tag}'], b[f'act_{tag}']
+        qkv, ao, fa, xmid, h, fm = (b[f'{k}_{s}'] for k in ('qkv', 'ao', 'fa', 'xmid', 'h', 'fm'))
+        df, dh, dxn, dao, dqkv, stats = (ws[k] for k in ('df', 'dh', 'dxn', 'dao', 'dqkv', 'stats'))
+        dxp = dx.data_ptr()
+        none = F32EPI_NONE
+        # --- MLP branch: x_out = x_mid + g2 * fc2(gelu(fc1(xn2)))
+        g.add('mdt_gate_bwd_f32', dxp, fm.data_ptr(), g2, NM, rows, df.data_ptr(), dg2, NM, M, W)
+        g.add('mdt_gelu_f32', h.data_ptr(), act.data_ptr(), M * 4 * W)
+        self._tn32(df, W, act, 4 * W, M, W, 4 * W, Gn('mlp.fc2.weight'), 4 * W)
+        self._cs32(df, W, Gn('mlp.fc2.bias'), M, W)
+        self._g32(df, W, Pf('mlp.fc2.weight'), 4 * W, M, 4 * W, W, dh, 4 * W, epi=none, b_kmajor=1, to=g)
+        g.add('mdt_gelu_bwd_f32', dh.data_ptr(), h.data_ptr(), dh.data_ptr(), M * 4 * W)
+        g.add('mdt_ln_modulate_f32', xmid.data_ptr(), sh2, sc2, NM, rows, xn.data_ptr(), M, W)
+        self._tn32(dh, 4 * W, xn, W, M, 4 * W, W, Gn('mlp.fc1.weight'), W)
+        self._cs32(dh, 4 * W, Gn('mlp.fc1.bias'), M, 4 * W)
+        self._g32(dh, 4 * W, Pf('mlp.fc1.weight'), W, M, W, 4 * W, dxn, W, epi=none, b_kmajor=1, to=g)
+        g.add('mdt_ln_modulate_bwd_f32', dxn.data_ptr(), xmid.data_ptr(), sc2, NM, rows, dxp, 1, dsh2, dsc2, NM, stats.data_ptr(), M, W)
+        # --- attention branch: x_mid = x_in + g1 * proj(attn(qkv(xn1)))
+        g.add('mdt_gate_bwd_f32', dxp, fa.data_ptr(), g1, NM, rows, df.data_ptr(), dg1, NM, M, W)
+        self._tn32(df, W, ao, W, M, W, W, Gn('attn.proj.weight'), W)
+        self._cs32(df, W, Gn('attn.proj.bias'), M, W)
+        self._g32(df, W, Pf('attn.proj.weight'), W, M, W, W, dao, W, epi=none, b_kmajor=1, to=g)
+        g.add('mdt_attn_f32_bwd', qkv.data_ptr(), dao.data_ptr(), ws['at'][0], ws['at'][1], dqkv.data_ptr(), B, rows, heads, hd)
+        g.add('mdt_ln_modulate_f32', x_in.data_ptr(), sh1, sc1, NM, rows, xn.data_ptr(), M, W)
+        self._tn32(dqkv, 3 * W, xn, W, M, 3 * W, W, Gn('attn.qkv.weight'), W)
+        self._cs32(dqkv, 3 * W, Gn('attn.qkv.bias'), M, 3 * W)
+        self._g32(dqkv, 3 * W, Pf('attn.qkv.weight'), W, M, W, 3 * W, dxn, W, epi=none, b_kmajor=1, to=g)
+        g.add('mdt_ln_modulate_bwd_f32', dxn.data_ptr(), x_in.data_ptr(), sc1, NM, rows, dxp, 1, dsh1, dsc1, NM, stats.data_ptr(), M, W)
+
     def _g32(self, A, lda, Bw, ldb, M, N, K, out, ldo, bias=0, epi=F32EPI_NONE, res=None, ldres=0, gate=0, gate_ld=0, rps=1,
-             b_kmajor=0, batch=0, heads=0, a_s=(0, 0), b_s=(0, 0), o_s=(0, 0)):
+             b_kmajor=0, batch=0, heads=0, a_s=(0, 0), b_s=(0, 0), o_s=(0, 0), to=None):
         """One mdt_gemm_f32 launch -- mdt_gemm_bf16x3 for a Linear layer of a 'bf16x3' plan; A / out / res are tensors or
         raw addresses, Bw / bias / gate raw addresses."""
         ptr = lambda t: t if isinstance(t, int) else t.data_ptr()  # noqa: E731
@@ -791,7 +1063,7 @@ class PassPlan:
         a.b_stride_b, a.b_stride_h = b_s
         a.o_stride_b, a.o_stride_h = o_s
         x3 = self.precision == 'bf16x3' and batch <= 1 and not b_kmajor
-        self.fwd.add('mdt_gemm_bf16x3' if x3 else 'mdt_gemm_f32', C.byref(self._k(a)))
+        (to or self.fwd).add('mdt_gemm_bf16x3' if x3 else 'mdt_gemm_f32', C.byref(self._k(a)))
 
     def _block_fwd_f32(self, prefix, tag, i, x_in, mod, moff, W, heads, rows, M):
         """DiTBlock.forward (models/maskdit.py:188-192) in fp32; all blocks of a stack share one buffer set."""

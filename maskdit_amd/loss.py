@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import call
-from .precond import EDMPrecond, _fill_plan_inputs, _ids32_from_dict, _stream, get_mask
+from .precond import MASKED_FP32_MESSAGE, EDMPrecond, _fill_plan_inputs, _ids32_from_dict, _stream, get_mask
 
 
 def unwrap_model(model):
@@ -39,7 +39,7 @@ class _LossFn(torch.autograd.Function):
         masked = mask_dict is not None
         L = mask_dict['ids_keep'].shape[1] if masked else None
         need_grad = bool(need_grad)
-        pl = eng.plan(B, masked, need_grad, L)
+        pl = eng.plan(B, masked, need_grad, L, net._train_plan_precision(masked))
         st = _stream()
         yn = pl.f32('yn', B, sp.C, sp.R, sp.R)
         D = pl.f32('D', B, sp.C, sp.R, sp.R)
@@ -104,6 +104,8 @@ class EDMLoss:
         noise = torch.randn_like(images)
         labels = raw._labels(labels, B, images.device).contiguous()
         mask_dict = None
+        if mask_ratio > 0 and raw.train_precision == 'fp32':
+            raise NotImplementedError(MASKED_FP32_MESSAGE)
         if mask_ratio > 0:
             assert raw.training, 'mask_ratio > 0 requires train mode (train_utils/loss.py:46)'
             mask_dict = get_mask(B, sp.T, mask_ratio, images.device)  # maskdit.py:476-477 (drawn after the noises)

@@ -25,6 +25,12 @@ from ._lib import call
 from .engine import MODEL_CONFIGS, Engine, Spec, check_precision, make_spec
 
 
+TRAIN_PRECISIONS = ('bf16', 'fp32')
+MASKED_FP32_MESSAGE = ("fp32 training (train precision 'fp32', train.py --no_amp) covers the UNMASKED stage only (mask_ratio 0: the "
+                       "reference's finetune-with-unmasking stage); the masked stage (mask_ratio > 0) trains with the bf16 kernels "
+                       "(set_train_precision('bf16'), no --no_amp)")
+
+
 # ------------------------------------------------------------------------------------------
 # fixed 2-D sin/cos positional table (models/maskdit.py:595-642)
 
@@ -220,6 +226,10 @@ class EDMPrecond(nn.Module):
         # (csrc/f32path.hip), what the reference's own sampler runs (sample.py:56, no autocast in generate.py); 'bf16x3' = that
         # plan with its Linear layers on mdt_gemm_bf16x3.
         self.eval_precision = 'bf16'
+        # arithmetic of TRAINING evaluations (a forward with gradient buffers, Losses['edm']): 'bf16' = the bf16 kernels
+        # (the reference under autocast); 'fp32' = exact fp32 forward and backward (csrc/f32train.hip), what the reference's
+        # `train.py --no_amp` runs -- provided for the unmasked stage (mask_ratio 0) only
+        self.train_precision = 'bf16'
 
     # ---- engine binding ------------------------------------------------------------------
     def _apply(self, fn, *a, **k):
@@ -289,6 +299,7 @@ class EDMPrecond(nn.Module):
                 p.requires_grad_(src[name].requires_grad)
         new.train(self.training)
         new.eval_precision = self.eval_precision
+        new.train_precision = self.train_precision
         memo[id(self)] = new
         return new
 
@@ -300,6 +311,23 @@ class EDMPrecond(nn.Module):
         fp32 plan with its Linear layers on the bf16 matrix instruction through a three-term split of every operand)."""
         self.eval_precision = check_precision(precision)
         return self
+
+    def set_train_precision(self, precision: str):
+        """'bf16' (default: bf16 matrix operands, fp32 residual stream and master weights) or 'fp32' (exact fp32 forward and
+        backward from the master weights: the reference's `--no_amp`).  'fp32' covers the unmasked stage: a training
+        evaluation with mask_ratio > 0 then raises NotImplementedError."""
+        if precision not in TRAIN_PRECISIONS:
+            raise ValueError(f"train precision must be one of {', '.join(map(repr, TRAIN_PRECISIONS))}, got {precision!r}")
+        self.train_precision = precision
+        return self
+
+    def _train_plan_precision(self, masked: bool) -> str:
+        """Plan precision of a training evaluation; refuses what the fp32 route does not cover."""
+        if self.train_precision != 'fp32':
+            return 'bf16'
+        if masked:
+            raise NotImplementedError(MASKED_FP32_MESSAGE)
+        return 'fp32'
 
     # ---- gradient plumbing ---------------------------------------------------------------
     def _prepare_grad_arena(self):
@@ -405,7 +433,10 @@ class _NetFn(torch.autograd.Function):
         B = x.shape[0]
         chw = sp.C * sp.R * sp.R
         masked = ids32 is not None
-        prec = net.eval_precision if not (need_grad or masked) else 'bf16'  # training / masked forwards: bf16 kernels only
+        if need_grad:  # a training evaluation: bf16 kernels, or exact fp32 for the unmasked stage (set_train_precision)
+            prec = net._train_plan_precision(masked)
+        else:
+            prec = net.eval_precision if not masked else 'bf16'  # masked forwards: bf16 kernels only
         pl = eng.plan(B, masked, bool(need_grad), L, prec)
         st = _stream()
         coef = pl.buf['coef']

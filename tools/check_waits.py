@@ -74,6 +74,8 @@ WATCH = {
     # gemm_bf16x3_kernel: register-staged like gemm_f32_kernel (the operand split sits between the global loads and ds_write)
     'f32path.hip': [(r'gemm_f32_dma_kernel', 'generic'), (r'gemm_f32_kernel', 'generic'), (r'attn_f32_kernel', 'generic'),
                     (r'gemm_bf16x3_kernel', 'generic')],
+    # fp32 training: gemm_f32_tn_kernel is register-staged with hipcc-placed waits (no inline assembly in the file)
+    'f32train.hip': [(r'gemm_f32_tn_kernel', 'generic')],
 }
 
 

@@ -225,16 +225,36 @@ def parse(argv=None):
     ap.add_argument('--cfg_scale', type=float, default=None)
     add_sampler_args(ap)  # train.py:322-326
     ap.add_argument('--ref_path', default=None)
-    # train.py:305 of the reference: --no_amp = fp32 / TF32 training.  This engine's TRAINING kernels compute in bf16 with an fp32
-    # residual stream / fp32 master weights (the reference under autocast); an fp32 backward does not exist.  The flag is
-    # accepted so that a reference command line fails with a statement of what IS provided, not with an argparse usage error.
-    ap.add_argument('--no_amp', action='store_true', help='not provided: fp32 exists for inference only (generate.py --precision fp32)')
-    args = ap.parse_args(argv)
-    if args.no_amp:
-        ap.error('--no_amp (fp32 training) is not provided by maskdit_amd: training runs bf16 MFMA operands with fp32 accumulation, '
-                 "an fp32 residual stream and fp32 master weights; the fp32-faithful path covers inference (generate.py --precision fp32, "
-                 "edm_sampler(precision='fp32'))")
-    return args
+    # train.py:305 of the reference: --no_amp = fp32 / TF32 training, the arithmetic of its second stage ("finetune with
+    # unmasking", mask_ratio 0).  Here it selects the exact-fp32 forward and backward (EDMPrecond.set_train_precision('fp32')),
+    # which covers that unmasked stage: resolve_train_precision refuses a config whose mask-ratio schedule is ever > 0.
+    ap.add_argument('--no_amp', action='store_true',
+                    help='fp32 training (forward and backward in exact fp32) of the unmasked stage: needs mask_ratio 0')
+    return ap.parse_args(argv)
+
+
+def mask_ratio_max(cfg) -> float:
+    """Largest mask ratio the config's schedule ever produces (every schedule of get_mask_ratio_fn is monotone in the
+    training progress, so the maximum sits at one end)."""
+    mc = cfg.model
+    name = mc.get('mask_ratio_fn', 'constant')
+    fn = get_mask_ratio_fn(name, mc.mask_ratio, mc.get('mask_ratio_min', 0))
+    return float(mc.mask_ratio) if name == 'constant' else max(fn(0.0), fn(1.0))
+
+
+def resolve_train_precision(args, cfg) -> str:
+    """'bf16' without --no_amp (nothing changes); 'fp32' with it -- after checking, before any GPU work, that the run is the
+    stage fp32 training covers."""
+    if not getattr(args, 'no_amp', False):
+        return 'bf16'
+    mx = mask_ratio_max(cfg)
+    if mx > 0:
+        raise SystemExit(f'--no_amp: fp32 training covers the UNMASKED stage only (the finetune-with-unmasking stage, '
+                         f'mask_ratio 0), but the mask-ratio schedule of {args.config} reaches {mx:g} '
+                         f"(mask_ratio {cfg.model.mask_ratio}, mask_ratio_fn {cfg.model.get('mask_ratio_fn', 'constant')}).  Train the "
+                         'masked stage without --no_amp (bf16 kernels), then finetune with a mask_ratio 0 config '
+                         '(configs/xl2-256-finetune-synthetic.yaml) and --no_amp.')
+    return 'fp32'
 
 
 def make_batches(cfg, args, dev, rank, world, B):
@@ -275,6 +295,7 @@ def train_loop(args):
 
 def _train_loop(args, state):
     cfg = load_config(args.config)
+    train_precision = resolve_train_precision(args, cfg)  # (--no_amp on a masked config ends here, before the GPU is touched)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -298,6 +319,8 @@ def _train_loop(args, state):
     net = M.Precond_models[mc.precond](img_resolution=mc.in_size, img_channels=mc.in_channels, num_classes=mc.num_classes,
                                        model_type=mc.model_type, use_decoder=mc.use_decoder, mae_loss_coef=mc.mae_loss_coef,
                                        pad_cls_token=mc.pad_cls_token, ext_feature_dim=mc.get('ext_feature_dim', 0)).to(dev)
+    if train_precision != 'bf16':
+        net.set_train_precision(train_precision)
     ema = copy.deepcopy(net).eval()
     for p in ema.parameters():
         p.requires_grad_(False)
@@ -369,6 +392,10 @@ def _train_loop(args, state):
         print(f'{mc.model_type} params {sum(p.numel() for p in net.parameters()):,}  global batch {global_batch} '
               f'({world} GPU x {mb} x accum {accum})  steps {step0} -> {step0 + max_steps}'
               + ('  [ZeRO-1]' if zero1 else '') + (f'  [gradient wire {wire}]' if world > 1 else ''), flush=True)
+        if train_precision == 'fp32':
+            print('--no_amp: exact fp32 forward and backward from the fp32 master weights (unmasked stage)'
+                  + (f'; train.tf32={tc.tf32} is read and ignored: there is no TF32 on this device, and fp32 is the tighter '
+                     'arithmetic' if 'tf32' in tc else ''), flush=True)
 
     batches = make_batches(cfg, args, dev, rank, world, mb * accum)
     step, log_steps, running = step0, 0, torch.zeros((), device=dev)
