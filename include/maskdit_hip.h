@@ -164,7 +164,10 @@ int mdt_mask_sort(const float* noise, int B, int T, int len_keep, int64_t* ids_s
 
 /* PatchEmbed (Conv2d k=s=p as a per-patch linear) + pos_embed + mask_out_token gather
  * (models/maskdit.py:116-127,278,475-483).  x [B,C,R,R] f32, scale[b] (c_in) optional,
- * W [D, C*p*p] f32, ids32 shuffle (NULL = all T tokens) -> out f32 [B, L, D]. */
+ * W [D, C*p*p] f32, ids32 shuffle (NULL = all T tokens) -> out f32 [B, L, D].
+ * Domain: R % p == 0 and C*p*p <= 16 (patch 2: per-thread products) or C*p*p = 64 / 256 (patch 4 / 8 at C = 4:
+ * the product on the fp32 matrix instruction; needs D % 32 == 0 and a 16-byte aligned W); anything else is refused.
+ * The backward ADDS into dW [D, C*p*p] and dbias [D] (gradient-arena semantics). */
 int mdt_patch_embed_fwd(const float* x, const float* in_scale, const float* W, const float* bias,
                         const float* pos, const int32_t* ids, int ids_ld, float* out, int B, int C,
                         int R, int p, int L, int D, mdt_stream_t stream);
@@ -190,7 +193,10 @@ int mdt_unmask_bwd(const float* dout, const int32_t* shuffle, int ids_ld, mdt_bf
                    float* dmask_token, int B, int T, int L, int Dd, int L_pitch, mdt_stream_t stream);
 
 /* FinalLayer + unpatchify (models/maskdit.py:216-234,411-424): x f32 [B*T, Dd] ->
- * LN-modulate -> Linear(Dd -> p*p*C) -> F [B,C,R,R] f32. */
+ * LN-modulate -> Linear(Dd -> p*p*C) -> F [B,C,R,R] f32; stats [B*T, 2] = (mean, rstd) per row for the backward.
+ * Domain: Dd <= 512; p*p*C <= 16 (Dd % 4 == 0) or p*p*C = 64 / 256 (T a square, Dd % 32 == 0, 16-byte aligned rows;
+ * the backward then runs as three launches and uses dx as its scratch); anything else is refused.
+ * The backward stores dx and ADDS into dW [p*p*C, Dd], dbias, dshift[b] and dscale[b]. */
 int mdt_final_fwd(const float* x, const float* shift, const float* scale, int mod_ld, const float* W,
                   const float* bias, float* F, float* stats, int B, int T, int Dd, int C, int p,
                   mdt_stream_t stream);
@@ -208,7 +214,8 @@ int mdt_edm_prep(const float* y, const float* rnd_normal, const float* noise, fl
                  float* xin, int B, int chw, float P_mean, float P_std, float sigma_data,
                  mdt_stream_t stream);
 /* D = c_skip*yn + c_out*F; per-sample loss (train_utils/loss.py:44-52,88-101).  mask NULL =>
- * plain mean.  */
+ * plain mean.  Domain: R % p == 0 and C*p*p <= 16 (a thread per patch) or C*p*p = 64 / 256 (a wave per patch);
+ * anything else is refused. */
 int mdt_edm_loss_fwd(const float* F, const float* yn, const float* y, const float* coef,
                      const float* mask, float mae_coef, float* D, float* loss, int B, int C, int R,
                      int p, mdt_stream_t stream);

@@ -7,6 +7,7 @@
 // FinalLayer (:216-234), unpatchify (:411-424).
 #include "common.h"
 #include "../../include/maskdit_hip.h"
+#include "patch_wide.h"
 
 #define PE_TOK 8      // tokens per workgroup in patch_embed_fwd
 #define MAX_PV 64     // max C*p*p supported (4*2*2 = 16 on the shipped configs)
@@ -464,7 +465,10 @@ extern "C" int mdt_patch_embed_fwd(const float* x, const float* in_scale, const 
                                    const float* pos, const int32_t* ids, int ids_ld, float* out, int B, int C, int R,
                                    int p, int L, int D, mdt_stream_t stream) {
   MDT_REQUIRE(x && W && bias && pos && out, "patch_embed_fwd: null pointer");
-  MDT_REQUIRE(C * p * p <= MAX_PV && R % p == 0, "patch_embed_fwd: unsupported patch geometry");
+  MDT_REQUIRE(p > 0 && R % p == 0 && (C * p * p <= 16 || mdt_wide_patch(C, p)),
+              "patch_embed_fwd: C*p*p must be <= 16, 64 or 256 and R a multiple of p");
+  if (C * p * p > 16)  // patch 4 / 8: the matrix-pipe form of patch.hip
+    return mdt_wide_patch_embed_fwd(x, in_scale, W, bias, pos, ids, ids_ld, out, B, C, R, p, L, D, (hipStream_t)stream);
   dim3 grid(cdiv(L, PE_TOK), B);
   hipLaunchKernelGGL(patch_embed_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, in_scale, W, bias, pos, ids,
                      ids_ld, out, C, R, p, L, D);
@@ -475,7 +479,10 @@ extern "C" int mdt_patch_embed_bwd(const float* x, const float* in_scale, const 
                                    int ids_ld, float* dW, float* dbias, int B, int C, int R, int p, int L, int D,
                                    mdt_stream_t stream) {
   MDT_REQUIRE(x && dout && dW && dbias, "patch_embed_bwd: null pointer");
-  MDT_REQUIRE(C * p * p <= 16 && R % p == 0, "patch_embed_bwd: C*p*p must be <= 16");
+  MDT_REQUIRE(p > 0 && R % p == 0 && (C * p * p <= 16 || mdt_wide_patch(C, p)),
+              "patch_embed_bwd: C*p*p must be <= 16, 64 or 256 and R a multiple of p");
+  if (C * p * p > 16)
+    return mdt_wide_patch_embed_bwd(x, in_scale, dout, ids, ids_ld, dW, dbias, B, C, R, p, L, D, (hipStream_t)stream);
   dim3 grid(cdiv((long)B * L, 64 * PE_CHUNKS), cdiv(D, 256));
   hipLaunchKernelGGL(patch_embed_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, in_scale, dout, ids, ids_ld,
                      dW, dbias, B, C, R, p, L, D);
@@ -536,7 +543,10 @@ extern "C" int mdt_final_fwd(const float* x, const float* shift, const float* sc
                              const float* bias, float* F, float* stats, int B, int T, int Dd, int C, int p,
                              mdt_stream_t stream) {
   MDT_REQUIRE(x && shift && scale && W && bias && F && stats, "final_fwd: null pointer");
-  MDT_REQUIRE(Dd % 4 == 0 && Dd <= FV * 256 && p * p * C <= FO, "final_fwd: needs Dd <= 512 and p*p*C <= 16");
+  MDT_REQUIRE(p > 0 && (p * p * C <= FO || mdt_wide_patch(C, p)), "final_fwd: p*p*C must be <= 16, 64 or 256");
+  if (p * p * C > FO)  // patch 4 / 8: the matrix-pipe form of patch.hip
+    return mdt_wide_final_fwd(x, shift, scale, mod_ld, W, bias, F, stats, B, T, Dd, C, p, (hipStream_t)stream);
+  MDT_REQUIRE(Dd % 4 == 0 && Dd <= FV * 256, "final_fwd: needs Dd <= 512, a multiple of 4");
   hipLaunchKernelGGL(final_fwd_kernel, dim3(cdiv((long)B * T, 4)), dim3(256), 0, (hipStream_t)stream, x, shift, scale,
                      mod_ld, W, bias, F, stats, B, T, Dd, C, p);
   return mdt_check_launch("final_fwd");
@@ -547,7 +557,11 @@ extern "C" int mdt_final_bwd(const float* dF, const float* x, const float* stats
                              float* dshift, float* dscale, int dmod_ld, int B, int T, int Dd, int C, int p,
                              mdt_stream_t stream) {
   MDT_REQUIRE(dF && x && stats && shift && scale && W && dx && dW && dbias && dshift && dscale, "final_bwd: null pointer");
-  MDT_REQUIRE(Dd % 4 == 0 && Dd <= FV * 256 && p * p * C <= FO, "final_bwd: needs Dd <= 512 and p*p*C <= 16");
+  MDT_REQUIRE(p > 0 && (p * p * C <= FO || mdt_wide_patch(C, p)), "final_bwd: p*p*C must be <= 16, 64 or 256");
+  if (p * p * C > FO)
+    return mdt_wide_final_bwd(dF, x, stats, shift, scale, mod_ld, W, dx, dW, dbias, dshift, dscale, dmod_ld, B, T, Dd, C, p,
+                              (hipStream_t)stream);
+  MDT_REQUIRE(Dd % 4 == 0 && Dd <= FV * 256, "final_bwd: needs Dd <= 512, a multiple of 4");
   int splits = 1;
   while (B * splits < 1024 && T / (splits * 2) >= 16) splits *= 2;
   int chunk = cdiv(T, splits);

@@ -5,6 +5,7 @@
 // EDMPrecond.forward coefficients (models/maskdit.py:756-773).
 #include "common.h"
 #include "../../include/maskdit_hip.h"
+#include "patch_wide.h"
 
 // coef is stored component-major: coef[i * B + b], i in (c_skip, c_out, c_in, c_noise, weight, sigma, -, -)
 #define NCOEF 8
@@ -220,7 +221,10 @@ extern "C" int mdt_edm_loss_fwd(const float* F, const float* yn, const float* y,
                                 float mae_coef, float* D, float* loss, int B, int C, int R, int p,
                                 mdt_stream_t stream) {
   MDT_REQUIRE(F && yn && y && coef && D && loss, "edm_loss_fwd: null pointer");
-  MDT_REQUIRE(C * p * p <= MAXP && R % p == 0, "edm_loss_fwd: unsupported patch geometry");
+  MDT_REQUIRE(p > 0 && R % p == 0 && (C * p * p <= 16 || mdt_wide_patch(C, p)),
+              "edm_loss_fwd: C*p*p must be <= 16, 64 or 256 and R a multiple of p");
+  if (C * p * p > 16)  // patch 4 / 8: a wave per patch (patch.hip)
+    return mdt_wide_edm_loss_fwd(F, yn, y, coef, mask, mae_coef, D, loss, B, C, R, p, (hipStream_t)stream);
   hipLaunchKernelGGL(edm_loss_fwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, F, yn, y, coef, mask, mae_coef, D,
                      loss, C, R, p);
   return mdt_check_launch("edm_loss_fwd");
@@ -230,7 +234,10 @@ extern "C" int mdt_edm_loss_bwd(const float* dloss, const float* D, const float*
                                 const float* coef, const float* mask, float mae_coef, float* dF, int B, int C, int R,
                                 int p, mdt_stream_t stream) {
   MDT_REQUIRE(dloss && D && yn && y && coef && dF, "edm_loss_bwd: null pointer");
-  MDT_REQUIRE(C * p * p <= MAXP && R % p == 0, "edm_loss_bwd: unsupported patch geometry");
+  MDT_REQUIRE(p > 0 && R % p == 0 && (C * p * p <= 16 || mdt_wide_patch(C, p)),
+              "edm_loss_bwd: C*p*p must be <= 16, 64 or 256 and R a multiple of p");
+  if (C * p * p > 16)
+    return mdt_wide_edm_loss_bwd(dloss, D, yn, y, coef, mask, mae_coef, dF, B, C, R, p, (hipStream_t)stream);
   hipLaunchKernelGGL(edm_loss_bwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, dloss, D, yn, y, coef, mask,
                      mae_coef, dF, C, R, p);
   return mdt_check_launch("edm_loss_bwd");

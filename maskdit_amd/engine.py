@@ -122,11 +122,14 @@ def make_spec(model_type, img_resolution, img_channels, num_classes, use_decoder
     sp = Spec(model_type, depth, D, heads, p, img_resolution, img_channels, num_classes, mae_loss_coef > 0)
     if sp.hd not in (32, 64, 72, 80):
         raise NotImplementedError(f'head_dim {sp.hd} unsupported')
-    if sp.pp > 16 or sp.num_classes > YPAD or sp.num_classes <= 0:
-        raise NotImplementedError('patch vector > 16 elements or num_classes outside (0, 1024]')
+    # the token-boundary kernels serve patch vectors of 16 elements (embed.hip / loss.hip) and of 64 and 256 (patch.hip)
+    if sp.pp not in (16, 64, 256) or sp.num_classes > YPAD or sp.num_classes <= 0:
+        raise NotImplementedError(f'patch vector of {sp.pp} elements (supported: 16, 64, 256 = 4 channels at patch 2, 4, 8) '
+                                  'or num_classes outside (0, 1024]')
     T = sp.T
-    if T & (T - 1) or T > 1024 or T % 64:
-        raise NotImplementedError(f'token count {T} must be a power of two in [64, 1024]')
+    if sp.R % p or T & (T - 1) or T > 1024 or T % 64:
+        raise NotImplementedError(f'token count {T} must be a power of two in [64, 1024]: patch {p} serves latent sides '
+                                  f'{8 * p}, {16 * p} and {32 * p} (the smallest is {8 * p})')
     return sp
 
 

@@ -195,7 +195,10 @@ class DiT(nn.Module):
 
 class EDMPrecond(nn.Module):
     """models/maskdit.py:722-776.  Constructor keywords follow the reference
-    (`train.py:123-131`, `generate.py:31-40`)."""
+    (`train.py:123-131`, `generate.py:31-40`).  `model_type` is any of the fifteen names of the reference's DiT_models
+    registry (S, B, L, XL, H at patch 2, 4, 8) on a 4-channel latent whose side gives 8, 16 or 32 tokens per side
+    (T = 64, 256, 1024): patch 2 at 16 / 32 / 64, patch 4 at 32 / 64 / 128, patch 8 at 64 / 128 / 256; engine.make_spec
+    refuses anything else and names the smallest side of the patch size."""
 
     def __init__(self, img_resolution, img_channels, num_classes=0, sigma_min=0, sigma_max=float('inf'), sigma_data=0.5,
                  model_type='DiT-B/2', use_decoder=True, mae_loss_coef=0.1, pad_cls_token=False, ext_feature_dim=0,
