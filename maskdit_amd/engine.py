@@ -237,9 +237,10 @@ class Layout:
 class Plan:
     """A replayable list of pre-marshalled launches (and optional python callbacks)."""
 
-    def __init__(self):
+    def __init__(self, listing: bool = False):
         self.calls: list = []
         self.keep: list = []
+        self.listing = listing  # built over HOST buffers (Engine.host_listing): to be read, never launched
 
     def add(self, name, *args):
         fn = getattr(_lib.lib(), name)
@@ -249,6 +250,8 @@ class Plan:
         self.calls.append((None, cb, 'callback'))
 
     def run(self, stream: int):
+        if self.listing:
+            raise _lib.MaskDiTLibError('this plan lists launches over host memory (Engine.host_listing): it cannot run')
         for fn, args, name in self.calls:
             if fn is None:
                 args()
@@ -261,10 +264,11 @@ class Plan:
 class Engine:
     """Owns arenas, shadows and launch plans for one EDMPrecond/DiT instance on one GPU."""
 
-    def __init__(self, sp: Spec, device):
+    def __init__(self, sp: Spec, device, _listing: bool = False):
         self.sp = sp
         self.device = torch.device(device)
-        if self.device.type != 'cuda':
+        self.listing = _listing
+        if self.device.type != 'cuda' and not _listing:
             raise _lib.MaskDiTLibError('maskdit_amd.Engine needs a CUDA/HIP device: there is no CPU path')
         _lib.lib()
         self.lay = Layout(sp)
@@ -289,6 +293,17 @@ class Engine:
         self.ema_applied = None
         LIVE_ENGINES.add(self)
 
+    @classmethod
+    def host_listing(cls, sp: Spec) -> 'Engine':
+        """An engine whose arenas are HOST tensors, for building PassPlan(eng, ...) where there is no GPU and reading its
+        launch lists (tools/plan_dump.py, tests/test_plan_lists_cpu.py).  Nothing built from it can launch: plan(),
+        refresh_shadows() and Plan.run() raise MaskDiTLibError."""
+        return cls(sp, 'cpu', _listing=True)
+
+    def _refuse_listing(self, what: str):
+        if self.listing:
+            raise _lib.MaskDiTLibError(f'{what} needs the device: this engine only lists plans over host memory')
+
     # ---- arenas ------------------------------------------------------------------------
     def view(self, arena: torch.Tensor, name: str) -> torch.Tensor:
         o, shp = self.lay.off[name], self.lay.shape[name]
@@ -302,6 +317,7 @@ class Engine:
     def refresh_shadows(self, cast: bool = True):
         """bf16 N-major shadow (optional: the optimizer already wrote it), K-major transposes,
         padded label table."""
+        self._refuse_listing('Engine.refresh_shadows')
         st = torch.cuda.current_stream().cuda_stream
         sp, lay = self.sp, self.lay
         if cast:
@@ -320,6 +336,7 @@ class Engine:
         depend on the padded count -- the exact one is a run-time argument of the four launches that read it
         (PassPlan.set_valid)."""
         global _PLAN_CLOCK
+        self._refuse_listing('Engine.plan')
         check_precision(precision)
         f32_train = precision == 'fp32' and train and not masked  # the unmasked stage (train.py --no_amp): _build_f32_train
         if reads_f32_arena(precision) and (masked or train) and not f32_train:
@@ -487,15 +504,17 @@ class PassPlan:
         self.lv_attn = C.c_int(self.Lv if masked else 0)
         self.Bp = _rup(B, 64)
         self.buf: Dict[str, torch.Tensor] = {}
-        self.fwd = Plan()
-        self.bwd = Plan()
+        self.fwd = Plan(eng.listing)
+        self.bwd = Plan(eng.listing)
         self.gen = 0  # forward generation: the saved activations belong to the LAST forward through this plan
-        if reads_f32_arena(precision) and train:
-            self._build_f32_train()
-        elif reads_f32_arena(precision):
-            self._build_f32()
-        else:
+        if train:
+            eng.ensure_grad()  # before a builder takes the first gradient address (Gf); inference plans need no gradient arena
+        if not reads_f32_arena(precision):
             self._build()
+        elif train:  # (Engine.plan lets only the unmasked stage at 'fp32' through)
+            self._build_f32_train()
+        else:
+            self._build_f32()
 
     @property
     def eng(self) -> Engine:
@@ -540,35 +559,51 @@ class PassPlan:
     def b16(self, name, *shape):
         return self.t(name, shape, torch.bfloat16)
 
+    # ---- addresses of one parameter (its full state-dict key) in the engine's arenas --------------
+    def Pf(self, name):
+        """fp32 master"""
+        return self.eng.P.data_ptr() + 4 * self.eng.lay.off[name]
+
+    def Gf(self, name):
+        """gradient (training plans: __init__ has made sure that the arena exists)"""
+        return self.eng.G.data_ptr() + 4 * self.eng.lay.off[name]
+
+    def Wp(self, name):
+        """bf16 N-major shadow"""
+        return self.eng.W16.data_ptr() + 2 * self.eng.lay.off[name]
+
+    def WT(self, key):
+        """bf16 K-major shadow ('ada': the stacked adaLN weight)"""
+        return self.eng.WT16.data_ptr() + 2 * self.eng.lay.t_off[key]
+
+    def _io(self):
+        """The buffers the callers fill and read, under the same names in every plan, so that the sampler, EDMPrecond.forward
+        and EDMLoss drive any of them the same way: 'xin', 'coef' (rows: c_skip, c_out, c_in, c_noise, weight, sigma, -, -;
+        'c_noise' is row 3), 'labels', 'ids32' (masked plans), 'F'.  EDMLoss's own buffers (loss.py; 16 KB per sample) are
+        allocated here too, so that they are covered by plan()'s out-of-memory handling like everything else: 'yn', 'D', 'y'
+        in every plan EDMLoss can be given (all but fp32 / bf16x3 inference), 'dF' in training plans.
+        Returns (xin, c_noise, labels, ids32 or None, F)."""
+        sp, B = self.eng.sp, self.B
+        img = (B, sp.C, sp.R, sp.R)
+        xin = self.f32('xin', *img)
+        cn = self.buf['c_noise'] = self.f32('coef', 8, B)[3]
+        lab = self.f32('labels', B, sp.num_classes)
+        ids32 = self.t('ids32', (B, 2 * self.T), torch.int32) if self.masked else None
+        Fx = self.f32('F', *img)
+        loss = ('yn', 'D', 'y') if self.train or not reads_f32_arena(self.precision) else ()
+        for nm in loss + (('dF',) if self.train else ()):
+            self.f32(nm, *img)
+        return xin, cn, lab, ids32, Fx
+
+    # ---- the bf16 plans (inference and training, masked or not) ------------------------------------
     def _build(self):
         eng, sp, lay = self.eng, self.eng.sp, self.eng.lay
         B, Bp, T, L, D, Dd = self.B, self.Bp, self.T, self.L, sp.D, sp.Dd
         NM = sp.n_mod
         train = self.train
-        Pp, W16p, WTp = eng.P.data_ptr(), eng.W16.data_ptr(), eng.WT16.data_ptr()
-
-        def Pf(name):  # fp32 master pointer
-            return Pp + 4 * lay.off[name]
-
-        def Wp(name):  # bf16 N-major shadow pointer
-            return W16p + 2 * lay.off[name]
-
-        def WT(key):  # bf16 K-major shadow pointer
-            return WTp + 2 * lay.t_off[key]
-
+        Pf, Wp, WT = self.Pf, self.Wp, self.WT
         f, g = self.fwd, self.bwd
-        # ---------------- inputs -----------------------------------------------------------
-        xin = self.f32('xin', B, sp.C, sp.R, sp.R)
-        coef = self.f32('coef', 8, B)  # rows: c_skip, c_out, c_in, c_noise, weight, sigma, -, -
-        cn = coef[3]
-        self.buf['c_noise'] = cn
-        lab = self.f32('labels', B, sp.num_classes)
-        ids32 = self.t('ids32', (B, 2 * T), torch.int32) if self.masked else None
-        Fx = self.f32('F', B, sp.C, sp.R, sp.R)
-        # EDMLoss's own buffers (loss.py; 16 KB per sample): allocated here so that they are covered by plan()'s
-        # out-of-memory handling like everything else
-        for nm in ('yn', 'D', 'y'):
-            self.f32(nm, B, sp.C, sp.R, sp.R)
+        xin, cn, lab, ids32, Fx = self._io()
         # ---------------- conditioning path ---------------------------------------------------
         temb = self.b16('temb', Bp, 256)
         h1, a1 = self.b16('h1', Bp, D), self.b16('a1', Bp, D)
@@ -577,18 +612,16 @@ class PassPlan:
         sc16 = self.b16('sc16', Bp, D)
         mod = self.f32('mod', Bp, NM)
         f.add('mdt_timestep_embed', cn.data_ptr(), temb.data_ptr(), 256, B, 256)
-        f.add('mdt_gemm_nt', C.byref(self._k(_nt(temb.data_ptr(), 256, Wp('model.t_embedder.mlp.0.weight'), 256, B, D, 256,
-                                               bias=Pf('model.t_embedder.mlp.0.bias'), epi=EPI_SILU, out=h1.data_ptr(), ldo=D,
-                                               out2=a1.data_ptr(), ldo2=D))))
-        f.add('mdt_gemm_nt', C.byref(self._k(_nt(a1.data_ptr(), D, Wp('model.t_embedder.mlp.2.weight'), D, B, D, D,
-                                               bias=Pf('model.t_embedder.mlp.2.bias'), epi=EPI_F32, outf=c_t.data_ptr(), ldof=D))))
+        self._nt16(f, temb.data_ptr(), 256, Wp('model.t_embedder.mlp.0.weight'), 256, B, D, 256,
+                   bias=Pf('model.t_embedder.mlp.0.bias'), epi=EPI_SILU, out=h1.data_ptr(), ldo=D, out2=a1.data_ptr(), ldo2=D)
+        self._nt16(f, a1.data_ptr(), D, Wp('model.t_embedder.mlp.2.weight'), D, B, D, D, bias=Pf('model.t_embedder.mlp.2.bias'),
+                   epi=EPI_F32, outf=c_t.data_ptr(), ldof=D)
         f.add('mdt_cast_f32_bf16', lab.data_ptr(), sp.num_classes, lab16.data_ptr(), YPAD, B, sp.num_classes, 0)
-        f.add('mdt_gemm_nt', C.byref(self._k(_nt(lab16.data_ptr(), YPAD, eng.Wy16.data_ptr(), YPAD, B, D, YPAD, epi=EPI_F32,
-                                               outf=c_y.data_ptr(), ldof=D))))
+        self._nt16(f, lab16.data_ptr(), YPAD, eng.Wy16.data_ptr(), YPAD, B, D, YPAD, epi=EPI_F32, outf=c_y.data_ptr(), ldof=D)
         f.add('mdt_add_f32', c_t.data_ptr(), c_y.data_ptr(), c.data_ptr(), B * D)
         f.add('mdt_cast_f32_bf16', c.data_ptr(), D, sc16.data_ptr(), D, B, D, 1)
-        f.add('mdt_gemm_nt', C.byref(self._k(_nt(sc16.data_ptr(), D, W16p + 2 * lay.ada_w, D, B, NM, D, bias=Pp + 4 * lay.ada_b,
-                                               epi=EPI_F32, outf=mod.data_ptr(), ldof=NM))))
+        self._nt16(f, sc16.data_ptr(), D, eng.W16.data_ptr() + 2 * lay.ada_w, D, B, NM, D, bias=eng.P.data_ptr() + 4 * lay.ada_b,
+                   epi=EPI_F32, outf=mod.data_ptr(), ldof=NM)
         # ---------------- encoder --------------------------------------------------------------
         Me = B * L
         x0 = self.f32('x_e0', Me, D)
@@ -615,8 +648,8 @@ class PassPlan:
         else:
             f.add('mdt_ln_modulate_fwd', xs_e[-1].data_ptr(), mod.data_ptr() + 4 * odl, mod.data_ptr() + 4 * (odl + D), NM, L,
                   xnd.data_ptr(), st_dl.data_ptr(), Me, D)
-        f.add('mdt_gemm_nt', C.byref(self._k(_nt(xnd.data_ptr(), D, Wp('model.decoder_layer.linear.weight'), D, Me, Dd, D,
-                                               bias=Pf('model.decoder_layer.linear.bias'), epi=EPI_BF16, out=xdec.data_ptr(), ldo=Dd))))
+        self._nt16(f, xnd.data_ptr(), D, Wp('model.decoder_layer.linear.weight'), D, Me, Dd, D,
+                   bias=Pf('model.decoder_layer.linear.bias'), epi=EPI_BF16, out=xdec.data_ptr(), ldo=Dd)
         Md = B * T
         xd0 = self.f32('x_d0', Md, Dd)
         use_mt = self.masked and sp.mae
@@ -636,13 +669,8 @@ class PassPlan:
         if not train:
             return
         # =================== backward ===========================================================
-        G = eng.ensure_grad()
-        Gp = G.data_ptr()
-
-        def Gf(name):
-            return Gp + 4 * lay.off[name]
-
-        dF = self.f32('dF', B, sp.C, sp.R, sp.R)
+        Gf, Gp = self.Gf, eng.G.data_ptr()
+        dF = self.buf['dF']
         dmod = self.f32('dmod', Bp, NM)
         wmax = max(Me * D, Md * Dd)
         dxe = self.f32('dx_e', Me, D)
@@ -658,21 +686,20 @@ class PassPlan:
               dmod.data_ptr() + 4 * (ofin + Dd), NM, B, T, Dd, sp.C, sp.patch)
         for i in reversed(range(sp.ddepth)):
             # the LN1 backward that ends block i also runs the MLP-gate backward that would open block i-1
-            nxt = self._gate_info(f'model.decoder_blocks.{i - 1}', 'd', i - 1, mod, dmod, sp.mod_off('dec', i - 1), Dd, Gf) \
+            nxt = self._gate_info(f'model.decoder_blocks.{i - 1}', 'd', i - 1, mod, dmod, sp.mod_off('dec', i - 1), Dd) \
                 if (i > 0 and FUSE_LN_GATE) else None
             self._block_bwd(f'model.decoder_blocks.{i}', 'd', i, xs_d[i], mod, dmod, sp.mod_off('dec', i), Dd, sp.dheads, T, Md,
-                            dxd, Gf, fuse_next=nxt, skip_first_gate=(FUSE_LN_GATE and i < sp.ddepth - 1))
+                            dxd, fuse_next=nxt, skip_first_gate=(FUSE_LN_GATE and i < sp.ddepth - 1))
             self._slab(f'dec{i}')
         dxdec = self.b16('dxdec', Me, Dd)
         g.add('mdt_unmask_bwd', dxd.data_ptr(), ids32.data_ptr() if self.masked else None, 2 * T, dxdec.data_ptr(),
               Gf('model.mask_token') if use_mt else None, B, T, self.lv_arg, Dd, L)
-        g.add('mdt_gemm_tn', C.byref(self._k(_tn(dxdec.data_ptr(), Dd, xnd.data_ptr(), D, Me, Dd, D,
-                                               Gf('model.decoder_layer.linear.weight'), D))))
+        self._tn16(g, dxdec.data_ptr(), Dd, xnd.data_ptr(), D, Me, Dd, D, Gf('model.decoder_layer.linear.weight'), D)
         g.add('mdt_colsum_bf16', dxdec.data_ptr(), Dd, Gf('model.decoder_layer.linear.bias'), Me, Dd)
-        g.add('mdt_gemm_nt', C.byref(self._k(_nt(dxdec.data_ptr(), Dd, WT('model.decoder_layer.linear.weight'), Dd, Me, D, Dd,
-                                               epi=EPI_BF16, out=ws['dxn'].data_ptr(), ldo=D))))
+        self._nt16(g, dxdec.data_ptr(), Dd, WT('model.decoder_layer.linear.weight'), Dd, Me, D, Dd, epi=EPI_BF16,
+                   out=ws['dxn'].data_ptr(), ldo=D)
         if FUSE_LN_GATE:
-            top = self._gate_info(f'model.blocks.{sp.depth - 1}', 'e', sp.depth - 1, mod, dmod, sp.mod_off('enc', sp.depth - 1), D, Gf)
+            top = self._gate_info(f'model.blocks.{sp.depth - 1}', 'e', sp.depth - 1, mod, dmod, sp.mod_off('enc', sp.depth - 1), D)
             g.add('mdt_ln_modulate_bwd_gate', ws['dxn'].data_ptr(), xs_e[-1].data_ptr(), st_dl.data_ptr(), mod.data_ptr() + 4 * (odl + D),
                   NM, L, dxe.data_ptr(), 0, dmod.data_ptr() + 4 * odl, dmod.data_ptr() + 4 * (odl + D), NM, Me, D, *top)
         else:
@@ -685,17 +712,16 @@ class PassPlan:
             n = r1 - r0
             g.add('mdt_cast_f32_bf16', dmod.data_ptr() + 4 * r0, NM, dmod16.data_ptr() + 2 * r0, NM, B, n, 0)
             g.add('mdt_colsum_bf16', dmod16.data_ptr() + 2 * r0, NM, Gp + 4 * (lay.ada_b + r0), B, n)
-            g.add('mdt_gemm_tn', C.byref(self._k(_tn(dmod16.data_ptr() + 2 * r0, NM, sc16.data_ptr(), D, Bp, n, D,
-                                                   Gp + 4 * (lay.ada_w + r0 * D), D))))
+            self._tn16(g, dmod16.data_ptr() + 2 * r0, NM, sc16.data_ptr(), D, Bp, n, D, Gp + 4 * (lay.ada_w + r0 * D), D)
             self._slab(name)
 
         groups = {name: (r0, r1) for name, r0, r1 in lay.ada_groups}
         ada_group('ada_w_dec', *groups['ada_w_dec'])  # final layer, decoder blocks, decoder layer: all done above
         self.marks['enc_bwd_begin'] = len(g.calls)  # everything from here on is encoder / conditioning-path backward
         for i in reversed(range(sp.depth)):
-            nxt = self._gate_info(f'model.blocks.{i - 1}', 'e', i - 1, mod, dmod, sp.mod_off('enc', i - 1), D, Gf) \
+            nxt = self._gate_info(f'model.blocks.{i - 1}', 'e', i - 1, mod, dmod, sp.mod_off('enc', i - 1), D) \
                 if (i > 0 and FUSE_LN_GATE) else None
-            self._block_bwd(f'model.blocks.{i}', 'e', i, xs_e[i], mod, dmod, sp.mod_off('enc', i), D, sp.heads, L, Me, dxe, Gf,
+            self._block_bwd(f'model.blocks.{i}', 'e', i, xs_e[i], mod, dmod, sp.mod_off('enc', i), D, sp.heads, L, Me, dxe,
                             fuse_next=nxt, skip_first_gate=FUSE_LN_GATE, lvalid=self.lv_attn)
             self._slab(f'enc{i}')
             if f'ada_w_enc{i}' in groups:  # block i is the lowest block of its group
@@ -708,58 +734,58 @@ class PassPlan:
         dh1 = self.b16('dh1', Bp, D)
         self._slab('ada_b')  # every group has written its part of the stacked adaLN bias gradient
         # M = batch, N = D, K = every modulation output (221 k on XL/2): split the contraction
-        g.add('mdt_gemm_nt', C.byref(self._k(_nt(dmod16.data_ptr(), NM, WT('ada'), NM, B, D, NM, epi=EPI_F32,
-                                               outf=dsc.data_ptr(), ldof=D,
-                                               k_splits=max(1, min(64, NM // 2048, 1024 // (((B + 127) // 128) * (D // 128))))))))
+        self._nt16(g, dmod16.data_ptr(), NM, WT('ada'), NM, B, D, NM, epi=EPI_F32, outf=dsc.data_ptr(), ldof=D,
+                   k_splits=max(1, min(64, NM // 2048, 1024 // (((B + 127) // 128) * (D // 128)))))
         g.add('mdt_silu_bwd', dsc.data_ptr(), c.data_ptr(), dc16.data_ptr(), B * D)
-        g.add('mdt_gemm_tn', C.byref(self._k(_tn(dc16.data_ptr(), D, lab16.data_ptr(), YPAD, Bp, D, YPAD,
-                                               Gf('model.y_embedder.embedding_table.weight'), sp.num_classes,
-                                               n1v=D, n2v=sp.num_classes))))
-        g.add('mdt_gemm_tn', C.byref(self._k(_tn(dc16.data_ptr(), D, a1.data_ptr(), D, Bp, D, D,
-                                               Gf('model.t_embedder.mlp.2.weight'), D))))
+        self._tn16(g, dc16.data_ptr(), D, lab16.data_ptr(), YPAD, Bp, D, YPAD, Gf('model.y_embedder.embedding_table.weight'),
+                   sp.num_classes, n1v=D, n2v=sp.num_classes)
+        self._tn16(g, dc16.data_ptr(), D, a1.data_ptr(), D, Bp, D, D, Gf('model.t_embedder.mlp.2.weight'), D)
         g.add('mdt_colsum_bf16', dc16.data_ptr(), D, Gf('model.t_embedder.mlp.2.bias'), B, D)
-        g.add('mdt_gemm_nt', C.byref(self._k(_nt(dc16.data_ptr(), D, WT('model.t_embedder.mlp.2.weight'), D, B, D, D,
-                                               epi=EPI_DSILU, out=dh1.data_ptr(), ldo=D, aux=h1.data_ptr(), ldaux=D))))
-        g.add('mdt_gemm_tn', C.byref(self._k(_tn(dh1.data_ptr(), D, temb.data_ptr(), 256, Bp, D, 256,
-                                               Gf('model.t_embedder.mlp.0.weight'), 256))))
+        self._nt16(g, dc16.data_ptr(), D, WT('model.t_embedder.mlp.2.weight'), D, B, D, D, epi=EPI_DSILU, out=dh1.data_ptr(), ldo=D,
+                   aux=h1.data_ptr(), ldaux=D)
+        self._tn16(g, dh1.data_ptr(), D, temb.data_ptr(), 256, Bp, D, 256, Gf('model.t_embedder.mlp.0.weight'), 256)
         g.add('mdt_colsum_bf16', dh1.data_ptr(), D, Gf('model.t_embedder.mlp.0.bias'), B, D)
         self._slab('misc')
 
-    # ---- the fp32-faithful inference plan (csrc/f32path.hip) ------------------------------------------------------
+    # ---- the fp32-faithful plans (csrc/f32path.hip, csrc/f32train.hip) -----------------------------
     def _build_f32(self):
         """The eval forward in EXACT fp32 -- what the reference's sampler runs (sample.py:56 `net(x_hat.float(), ...)`, no
         autocast in generate.py): fp32 master weights straight from the parameter arena (no bf16 shadow is read), fp32
         activations, fp32-input MFMA GEMMs (mdt_gemm_f32), attention as q k^T -> row softmax -> p v over the packed qkv
         buffer.  Same graph as _build (DiT.forward, models/maskdit.py:511-557, unmasked), same input / output buffers
-        ('xin', 'coef', 'labels', 'F'), so the sampler and EDMPrecond.forward drive either plan the same way.  Precision
-        'bf16x3' builds the same graph with every Linear layer on mdt_gemm_bf16x3 (see _g32)."""
+        (_io), so the sampler and EDMPrecond.forward drive either plan the same way.  Precision 'bf16x3' builds the same
+        graph with every Linear layer on mdt_gemm_bf16x3 (see _g32)."""
+        self._fwd_f32(save=False)
+
+    def _fwd_f32(self, save: bool):
+        """The fp32 forward, emitted once for both fp32 builders.  `save`: keep what a backward needs -- every block gets
+        buffers of its own (the inference plan shares one set per stack and ping-pongs the residual stream), and the
+        activations (SiLU of the timestep MLP, GELU) and gate + residual adds are passes of their own instead of GEMM
+        epilogues, so that the pre-activations h1 / h and the branch outputs survive.  Returns the residual-stream buffers
+        (xs_e, xs_d): input of encoder / decoder block i at [i], the stack's output last."""
         eng, sp, lay = self.eng, self.eng.sp, self.eng.lay
         B, T, D, Dd = self.B, self.T, sp.D, sp.Dd
         NM = sp.n_mod
-        assert not self.masked and not self.train
+        assert not self.masked
         if sp.num_classes % 4:
             raise NotImplementedError('fp32 path: num_classes must be a multiple of 4 (16-byte label rows)')
         if B * max(sp.heads, sp.dheads) > 65535:
             raise NotImplementedError('fp32 path: batch * heads must not exceed 65535 (one grid row per (sample, head))')
-        Pp = eng.P.data_ptr()
-
-        def Pf(name):
-            return Pp + 4 * lay.off[name]
-
+        Pf, Pp = self.Pf, eng.P.data_ptr()
         f = self.fwd
-        xin = self.f32('xin', B, sp.C, sp.R, sp.R)
-        coef = self.f32('coef', 8, B)
-        cn = coef[3]
-        self.buf['c_noise'] = cn
-        lab = self.f32('labels', B, sp.num_classes)
-        Fx = self.f32('F', B, sp.C, sp.R, sp.R)
+        xin, cn, lab, _, Fx = self._io()
         # ---------------- conditioning path (TimestepEmbedder :34-60, LabelEmbedder :75, SiLU + adaLN Linears :183-186)
         temb, a1 = self.f32('temb', B, 256), self.f32('a1', B, D)
         c_t, c, sc = self.f32('c_t', B, D), self.f32('c', B, D), self.f32('sc', B, D)
         mod = self.f32('mod', B, NM)
         f.add('mdt_timestep_embed_f32', cn.data_ptr(), temb.data_ptr(), 256, B, 256)
-        self._g32(temb, 256, Pf('model.t_embedder.mlp.0.weight'), 256, B, D, 256, a1, D, bias=Pf('model.t_embedder.mlp.0.bias'),
-                  epi=F32EPI_SILU)
+        if save:
+            h1 = self.f32('h1', B, D)
+            self._g32(temb, 256, Pf('model.t_embedder.mlp.0.weight'), 256, B, D, 256, h1, D, bias=Pf('model.t_embedder.mlp.0.bias'))
+            f.add('mdt_silu_f32', h1.data_ptr(), a1.data_ptr(), B * D)
+        else:
+            self._g32(temb, 256, Pf('model.t_embedder.mlp.0.weight'), 256, B, D, 256, a1, D, bias=Pf('model.t_embedder.mlp.0.bias'),
+                      epi=F32EPI_SILU)
         self._g32(a1, D, Pf('model.t_embedder.mlp.2.weight'), D, B, D, D, c_t, D, bias=Pf('model.t_embedder.mlp.2.bias'))
         # c = t_emb + y @ table^T (the one-hot / zero / soft label row times the embedding table)
         self._g32(lab, sp.num_classes, Pf('model.y_embedder.embedding_table.weight'), sp.num_classes, B, D, sp.num_classes, c, D,
@@ -767,27 +793,30 @@ class PassPlan:
         f.add('mdt_silu_f32', c.data_ptr(), sc.data_ptr(), B * D)
         self._g32(sc, D, Pp + 4 * lay.ada_w, D, B, NM, D, mod, NM, bias=Pp + 4 * lay.ada_b)
         # ---------------- encoder (all T tokens: masking applies in train mode only, models/maskdit.py:482,539) ---------
-        Me = B * T
-        x = self.f32('x_e0', Me, D)
+        M = B * T
+        xs_e = [self.f32('x_e0', M, D)]
         f.add('mdt_patch_embed_fwd', xin.data_ptr(), None, Pf('model.x_embedder.proj.weight'), Pf('model.x_embedder.proj.bias'),
-              eng.pos.data_ptr(), None, 2 * T, x.data_ptr(), B, sp.C, sp.R, sp.patch, T, D)
+              eng.pos.data_ptr(), None, 2 * T, xs_e[0].data_ptr(), B, sp.C, sp.R, sp.patch, T, D)
         for i in range(sp.depth):
-            x = self._block_fwd_f32(f'model.blocks.{i}', 'e', i, x, mod, sp.mod_off('enc', i), D, sp.heads, T, Me)
+            xs_e.append(self._block_fwd_f32(f'model.blocks.{i}', 'e', i, xs_e[-1], mod, sp.mod_off('enc', i), D, sp.heads, T, M, save))
         self.marks = {'enc_fwd_end': len(f.calls)}
         # ---------------- DecoderLayer (:195-213) + decoder_pos_embed (:545) -------------------------------------------
         odl = sp.mod_off('dl')
-        xnd, xdec = self.f32('xn_e', Me, D), self.f32('xdec', Me, Dd)
-        f.add('mdt_ln_modulate_f32', x.data_ptr(), mod.data_ptr() + 4 * odl, mod.data_ptr() + 4 * (odl + D), NM, T, xnd.data_ptr(), Me, D)
-        self._g32(xnd, D, Pf('model.decoder_layer.linear.weight'), D, Me, Dd, D, xdec, Dd, bias=Pf('model.decoder_layer.linear.bias'))
-        x = self.f32('x_d0', Me, Dd)
-        f.add('mdt_add_rows_f32', xdec.data_ptr(), eng.dpos.data_ptr(), x.data_ptr(), Me, T, Dd)
+        xn_e, xdec = self.f32('xn_e', M, D), self.f32('xdec', M, Dd)
+        f.add('mdt_ln_modulate_f32', xs_e[-1].data_ptr(), mod.data_ptr() + 4 * odl, mod.data_ptr() + 4 * (odl + D), NM, T,
+              xn_e.data_ptr(), M, D)
+        self._g32(xn_e, D, Pf('model.decoder_layer.linear.weight'), D, M, Dd, D, xdec, Dd, bias=Pf('model.decoder_layer.linear.bias'))
+        xs_d = [self.f32('x_d0', M, Dd)]
+        f.add('mdt_add_rows_f32', xdec.data_ptr(), eng.dpos.data_ptr(), xs_d[0].data_ptr(), M, T, Dd)
         for i in range(sp.ddepth):
-            x = self._block_fwd_f32(f'model.decoder_blocks.{i}', 'd', i, x, mod, sp.mod_off('dec', i), Dd, sp.dheads, T, Me)
+            xs_d.append(self._block_fwd_f32(f'model.decoder_blocks.{i}', 'd', i, xs_d[-1], mod, sp.mod_off('dec', i), Dd, sp.dheads, T, M,
+                                            save))
         ofin = sp.mod_off('fin')
-        st_f = self.f32('st_f', Me, 2)
-        f.add('mdt_final_fwd', x.data_ptr(), mod.data_ptr() + 4 * ofin, mod.data_ptr() + 4 * (ofin + Dd), NM,
+        st_f = self.f32('st_f', M, 2)
+        f.add('mdt_final_fwd', xs_d[-1].data_ptr(), mod.data_ptr() + 4 * ofin, mod.data_ptr() + 4 * (ofin + Dd), NM,
               Pf('model.final_layer.linear.weight'), Pf('model.final_layer.linear.bias'), Fx.data_ptr(), st_f.data_ptr(),
               B, T, Dd, sp.C, sp.patch)
+        return xs_e, xs_d
 
     # ---- fp32 training of the unmasked stage (csrc/f32train.hip) -----------------------------------------------------
     @staticmethod
@@ -828,96 +857,40 @@ class PassPlan:
 
     def _build_f32_train(self):
         """Forward + backward of the UNMASKED training step in exact fp32: the reference's second stage ("finetune with
-        unmasking", README.md:102-119: mask_ratio 0, train.py --no_amp).  The forward is _build_f32's graph with per-block
-        saved activations (and unfused GELU / gate + residual passes, so that the pre-activation h and the branch outputs
-        f survive); the backward is the hand-derived gradient of the same graph, filling the gradient arena the bf16 plan
-        fills with the same `+=` semantics.  Weights are read from the fp32 master arena: no bf16 shadow is involved.
-        LayerNorm outputs and GELU outputs are recomputed in the backward instead of being kept (12 instead of 18 floats
-        per token, block and channel)."""
+        unmasking", README.md:102-119: mask_ratio 0, train.py --no_amp).  The forward is _build_f32's graph, walked with
+        `save` (_fwd_f32); the backward is the hand-derived gradient of the same graph, filling the gradient arena the
+        bf16 plan fills with the same `+=` semantics.  Weights are read from the fp32 master arena: no bf16 shadow is
+        involved.  LayerNorm outputs and GELU outputs are recomputed in the backward instead of being kept (12 instead of
+        18 floats per token, block and channel).  (Engine.plan refuses the masked stage and 'bf16x3' before it gets here.)"""
         eng, sp, lay = self.eng, self.eng.sp, self.eng.lay
         B, T, D, Dd = self.B, self.T, sp.D, sp.Dd
         NM = sp.n_mod
-        if self.masked or self.precision != 'fp32':
-            raise NotImplementedError("fp32 training covers the unmasked stage at precision 'fp32' only")
-        if sp.num_classes % 4:
-            raise NotImplementedError('fp32 path: num_classes must be a multiple of 4 (16-byte label rows)')
-        if B * max(sp.heads, sp.dheads) > 65535:
-            raise NotImplementedError('fp32 path: batch * heads must not exceed 65535 (one grid row per (sample, head))')
-        Pp = eng.P.data_ptr()
-        Gp = eng.ensure_grad().data_ptr()
-
-        def Pf(name):
-            return Pp + 4 * lay.off[name]
-
-        def Gf(name):
-            return Gp + 4 * lay.off[name]
-
-        f, g = self.fwd, self.bwd
         M = B * T
-        xin = self.f32('xin', B, sp.C, sp.R, sp.R)
-        coef = self.f32('coef', 8, B)
-        cn = coef[3]
-        self.buf['c_noise'] = cn
-        lab = self.f32('labels', B, sp.num_classes)
-        Fx = self.f32('F', B, sp.C, sp.R, sp.R)
-        dF = self.f32('dF', B, sp.C, sp.R, sp.R)
-        for nm in ('yn', 'D', 'y'):  # EDMLoss's own buffers, as in _build
-            self.f32(nm, B, sp.C, sp.R, sp.R)
         # ---- workspaces shared by the whole backward: sized for the largest request ------------------------------------
         Wm = max(D, Dd)
         tn_floats, cs_floats, at_floats = self._f32_train_ws(sp, B)
         tnws = self.f32('ws_tn', max(tn_floats, 4))
         csws = self.f32('ws_colsum', max(cs_floats, 4))
         atws = self.f32('ws_attn', at_floats)
-        self._f32ws = dict(tn=(tnws.data_ptr(), tn_floats), cs=(csws.data_ptr(), cs_floats), at=(atws.data_ptr(), at_floats),
-                           df=self.f32('ws_df', M * Wm), dh=self.f32('ws_dh', 4 * M * Wm), dxn=self.f32('ws_dxn', M * Wm),
-                           dao=self.f32('ws_dao', M * Wm), dqkv=self.f32('ws_dqkv', 3 * M * Wm), stats=self.f32('ws_stats', 2 * M))
-        # ---------------- conditioning path -----------------------------------------------------------------------------
-        temb, h1, a1 = self.f32('temb', B, 256), self.f32('h1', B, D), self.f32('a1', B, D)
-        c_t, c, sc = self.f32('c_t', B, D), self.f32('c', B, D), self.f32('sc', B, D)
-        mod = self.f32('mod', B, NM)
-        f.add('mdt_timestep_embed_f32', cn.data_ptr(), temb.data_ptr(), 256, B, 256)
-        self._g32(temb, 256, Pf('model.t_embedder.mlp.0.weight'), 256, B, D, 256, h1, D, bias=Pf('model.t_embedder.mlp.0.bias'))
-        f.add('mdt_silu_f32', h1.data_ptr(), a1.data_ptr(), B * D)
-        self._g32(a1, D, Pf('model.t_embedder.mlp.2.weight'), D, B, D, D, c_t, D, bias=Pf('model.t_embedder.mlp.2.bias'))
-        self._g32(lab, sp.num_classes, Pf('model.y_embedder.embedding_table.weight'), sp.num_classes, B, D, sp.num_classes, c, D,
-                  epi=F32EPI_GATE_RES, res=c_t, ldres=D, rps=1)
-        f.add('mdt_silu_f32', c.data_ptr(), sc.data_ptr(), B * D)
-        self._g32(sc, D, Pp + 4 * lay.ada_w, D, B, NM, D, mod, NM, bias=Pp + 4 * lay.ada_b)
-        # ---------------- encoder -----------------------------------------------------------------------------------------
-        x = self.f32('x_e0', M, D)
-        f.add('mdt_patch_embed_fwd', xin.data_ptr(), None, Pf('model.x_embedder.proj.weight'), Pf('model.x_embedder.proj.bias'),
-              eng.pos.data_ptr(), None, 2 * T, x.data_ptr(), B, sp.C, sp.R, sp.patch, T, D)
-        xs_e = [x]
-        for i in range(sp.depth):
-            xs_e.append(self._block_fwd_f32t(f'model.blocks.{i}', 'e', i, xs_e[-1], mod, sp.mod_off('enc', i), D, sp.heads, T, M))
-        self.marks = {'enc_fwd_end': len(f.calls)}
-        odl = sp.mod_off('dl')
-        xn_e, xdec = self.f32('xn_e', M, D), self.f32('xdec', M, Dd)
-        f.add('mdt_ln_modulate_f32', xs_e[-1].data_ptr(), mod.data_ptr() + 4 * odl, mod.data_ptr() + 4 * (odl + D), NM, T,
-              xn_e.data_ptr(), M, D)
-        self._g32(xn_e, D, Pf('model.decoder_layer.linear.weight'), D, M, Dd, D, xdec, Dd, bias=Pf('model.decoder_layer.linear.bias'))
-        xd0 = self.f32('x_d0', M, Dd)
-        f.add('mdt_add_rows_f32', xdec.data_ptr(), eng.dpos.data_ptr(), xd0.data_ptr(), M, T, Dd)
-        xs_d = [xd0]
-        for i in range(sp.ddepth):
-            xs_d.append(self._block_fwd_f32t(f'model.decoder_blocks.{i}', 'd', i, xs_d[-1], mod, sp.mod_off('dec', i), Dd, sp.dheads, T, M))
-        ofin = sp.mod_off('fin')
-        st_f = self.f32('st_f', M, 2)
-        f.add('mdt_final_fwd', xs_d[-1].data_ptr(), mod.data_ptr() + 4 * ofin, mod.data_ptr() + 4 * (ofin + Dd), NM,
-              Pf('model.final_layer.linear.weight'), Pf('model.final_layer.linear.bias'), Fx.data_ptr(), st_f.data_ptr(),
-              B, T, Dd, sp.C, sp.patch)
+        self._f32ws = ws = dict(tn=(tnws.data_ptr(), tn_floats), cs=(csws.data_ptr(), cs_floats), at=(atws.data_ptr(), at_floats),
+                                df=self.f32('ws_df', M * Wm), dh=self.f32('ws_dh', 4 * M * Wm), dxn=self.f32('ws_dxn', M * Wm),
+                                dao=self.f32('ws_dao', M * Wm), dqkv=self.f32('ws_dqkv', 3 * M * Wm), stats=self.f32('ws_stats', 2 * M))
+        xs_e, xs_d = self._fwd_f32(save=True)
         # =================== backward =====================================================================================
+        Pf, Gf, Pp, Gp = self.Pf, self.Gf, eng.P.data_ptr(), eng.G.data_ptr()
+        g, b = self.bwd, self.buf
+        xin, lab, dF, temb, h1, a1, c, sc, mod, xn_e, st_f = (b[k] for k in ('xin', 'labels', 'dF', 'temb', 'h1', 'a1', 'c', 'sc', 'mod',
+                                                                              'xn_e', 'st_f'))
+        odl, ofin = sp.mod_off('dl'), sp.mod_off('fin')
         dmod = self.f32('dmod', B, NM)
         dxe, dxd = self.f32('dx_e', M, D), self.f32('dx_d', M, Dd)
-        ws = self._f32ws
         g.add_callback(lambda: dmod.zero_())  # (mdt_final_bwd adds its two modulation gradients; every other column is stored)
         g.add('mdt_final_bwd', dF.data_ptr(), xs_d[-1].data_ptr(), st_f.data_ptr(), mod.data_ptr() + 4 * ofin,
               mod.data_ptr() + 4 * (ofin + Dd), NM, Pf('model.final_layer.linear.weight'), dxd.data_ptr(),
               Gf('model.final_layer.linear.weight'), Gf('model.final_layer.linear.bias'), dmod.data_ptr() + 4 * ofin,
               dmod.data_ptr() + 4 * (ofin + Dd), NM, B, T, Dd, sp.C, sp.patch)
         for i in reversed(range(sp.ddepth)):
-            self._block_bwd_f32(f'model.decoder_blocks.{i}', 'd', i, xs_d[i], mod, dmod, sp.mod_off('dec', i), Dd, sp.dheads, T, M, dxd, Gf)
+            self._block_bwd_f32(f'model.decoder_blocks.{i}', 'd', i, xs_d[i], mod, dmod, sp.mod_off('dec', i), Dd, sp.dheads, T, M, dxd)
             self._slab(f'dec{i}')
         # x_d0 = xdec + decoder_pos_embed: d xdec = dx_d.  mask_token takes no part in an unmasked pass: its gradient stays
         # the zero _prepare_grad_arena wrote (train_utils/loss.py:57-58 adds 0 * mask_token.sum() for the same effect)
@@ -931,7 +904,7 @@ class PassPlan:
               dxe.data_ptr(), 0, dmod.data_ptr() + 4 * odl, dmod.data_ptr() + 4 * (odl + D), NM, ws['stats'].data_ptr(), M, D)
         self.marks['enc_bwd_begin'] = len(g.calls)
         for i in reversed(range(sp.depth)):
-            self._block_bwd_f32(f'model.blocks.{i}', 'e', i, xs_e[i], mod, dmod, sp.mod_off('enc', i), D, sp.heads, T, M, dxe, Gf)
+            self._block_bwd_f32(f'model.blocks.{i}', 'e', i, xs_e[i], mod, dmod, sp.mod_off('enc', i), D, sp.heads, T, M, dxe)
             self._slab(f'enc{i}')
         g.add('mdt_patch_embed_bwd', xin.data_ptr(), None, dxe.data_ptr(), None, 2 * T, Gf('model.x_embedder.proj.weight'),
               Gf('model.x_embedder.proj.bias'), B, sp.C, sp.R, sp.patch, T, D)
@@ -976,46 +949,14 @@ class PassPlan:
         wsp, wsn = self._f32ws['cs']
         self.bwd.add('mdt_colsum_f32', A.data_ptr(), ld, outp, wsp, wsn, M, N, 1)
 
-    def _block_fwd_f32t(self, prefix, tag, i, x_in, mod, moff, W, heads, rows, M):
-        """DiTBlock.forward (models/maskdit.py:188-192) in fp32, keeping what the backward needs: qkv, the attention output,
-        both branch outputs f (so the residual adds are passes of their own), x_mid and the pre-GELU h."""
-        eng, lay, f = self.eng, self.eng.lay, self.fwd
-        NM = eng.sp.n_mod
-        hd = W // heads
-        B = self.B
-        s = f'{tag}{i}'
-        Pp = eng.P.data_ptr()
-        Pf = lambda n: Pp + 4 * lay.off[f'{prefix}.{n}']  # noqa: E731
-        mp = mod.data_ptr()
-        sh1, sc1, g1, sh2, sc2, g2 = (mp + 4 * (moff + k * W) for k in range(6))
-        xn, act = self.f32(f'xn_{tag}', M, W), self.f32(f'act_{tag}', M, 4 * W)  # shared: recomputed by the backward
-        qkv, ao, fa = self.f32(f'qkv_{s}', M, 3 * W), self.f32(f'ao_{s}', M, W), self.f32(f'fa_{s}', M, W)
-        xmid, h, fm = self.f32(f'xmid_{s}', M, W), self.f32(f'h_{s}', M, 4 * W), self.f32(f'fm_{s}', M, W)
-        xout = self.f32(f'x_{tag}{i + 1}', M, W)
-        ws_floats = int(_lib.lib().mdt_attn_f32_ws_floats(B, rows, heads, hd))
-        S = self._f32ws['at'][0] if ws_floats else None  # (the backward's score workspace is at least twice as large)
-        f.add('mdt_ln_modulate_f32', x_in.data_ptr(), sh1, sc1, NM, rows, xn.data_ptr(), M, W)
-        self._g32(xn, W, Pf('attn.qkv.weight'), W, M, 3 * W, W, qkv, 3 * W, bias=Pf('attn.qkv.bias'))
-        f.add('mdt_attn_f32', qkv.data_ptr(), ao.data_ptr(), S, B, rows, heads, hd)
-        self._g32(ao, W, Pf('attn.proj.weight'), W, M, W, W, fa, W, bias=Pf('attn.proj.bias'))
-        f.add('mdt_gate_res_f32', x_in.data_ptr(), fa.data_ptr(), g1, NM, rows, xmid.data_ptr(), M, W)
-        f.add('mdt_ln_modulate_f32', xmid.data_ptr(), sh2, sc2, NM, rows, xn.data_ptr(), M, W)
-        self._g32(xn, W, Pf('mlp.fc1.weight'), W, M, 4 * W, W, h, 4 * W, bias=Pf('mlp.fc1.bias'))
-        f.add('mdt_gelu_f32', h.data_ptr(), act.data_ptr(), M * 4 * W)
-        self._g32(act, 4 * W, Pf('mlp.fc2.weight'), 4 * W, M, W, 4 * W, fm, W, bias=Pf('mlp.fc2.bias'))
-        f.add('mdt_gate_res_f32', xmid.data_ptr(), fm.data_ptr(), g2, NM, rows, xout.data_ptr(), M, W)
-        return xout
-
-    def _block_bwd_f32(self, prefix, tag, i, x_in, mod, dmod, moff, W, heads, rows, M, dx, Gf):
+    def _block_bwd_f32(self, prefix, tag, i, x_in, mod, dmod, moff, W, heads, rows, M, dx):
         """Backward of DiTBlock in fp32: dx (the residual-stream gradient) is updated in place."""
-        eng, lay, g, ws = self.eng, self.eng.lay, self.bwd, self._f32ws
-        NM = eng.sp.n_mod
+        g, ws = self.bwd, self._f32ws
+        NM = self.eng.sp.n_mod
         hd = W // heads
         B = self.B
         s = f'{tag}{i}'
-        Pp = eng.P.data_ptr()
-        Pf = lambda n: Pp + 4 * lay.off[f'{prefix}.{n}']  # noqa: E731
-        Gn = lambda n: Gf(f'{prefix}.{n}')  # noqa: E731
+        p, Pf, Gf = prefix + '.', self.Pf, self.Gf
         mp, dp = mod.data_ptr(), dmod.data_ptr()
         sh1, sc1, g1, sh2, sc2, g2 = (mp + 4 * (moff + k * W) for k in range(6))
         dsh1, dsc1, dg1, dsh2, dsc2, dg2 = (dp + 4 * (moff + k * W) for k in range(6))
@@ -1028,25 +969,25 @@ class PassPlan:
         # --- MLP branch: x_out = x_mid + g2 * fc2(gelu(fc1(xn2)))
         g.add('mdt_gate_bwd_f32', dxp, fm.data_ptr(), g2, NM, rows, df.data_ptr(), dg2, NM, M, W)
         g.add('mdt_gelu_f32', h.data_ptr(), act.data_ptr(), M * 4 * W)
-        self._tn32(df, W, act, 4 * W, M, W, 4 * W, Gn('mlp.fc2.weight'), 4 * W)
-        self._cs32(df, W, Gn('mlp.fc2.bias'), M, W)
-        self._g32(df, W, Pf('mlp.fc2.weight'), 4 * W, M, 4 * W, W, dh, 4 * W, epi=none, b_kmajor=1, to=g)
+        self._tn32(df, W, act, 4 * W, M, W, 4 * W, Gf(p + 'mlp.fc2.weight'), 4 * W)
+        self._cs32(df, W, Gf(p + 'mlp.fc2.bias'), M, W)
+        self._g32(df, W, Pf(p + 'mlp.fc2.weight'), 4 * W, M, 4 * W, W, dh, 4 * W, epi=none, b_kmajor=1, to=g)
         g.add('mdt_gelu_bwd_f32', dh.data_ptr(), h.data_ptr(), dh.data_ptr(), M * 4 * W)
         g.add('mdt_ln_modulate_f32', xmid.data_ptr(), sh2, sc2, NM, rows, xn.data_ptr(), M, W)
-        self._tn32(dh, 4 * W, xn, W, M, 4 * W, W, Gn('mlp.fc1.weight'), W)
-        self._cs32(dh, 4 * W, Gn('mlp.fc1.bias'), M, 4 * W)
-        self._g32(dh, 4 * W, Pf('mlp.fc1.weight'), W, M, W, 4 * W, dxn, W, epi=none, b_kmajor=1, to=g)
+        self._tn32(dh, 4 * W, xn, W, M, 4 * W, W, Gf(p + 'mlp.fc1.weight'), W)
+        self._cs32(dh, 4 * W, Gf(p + 'mlp.fc1.bias'), M, 4 * W)
+        self._g32(dh, 4 * W, Pf(p + 'mlp.fc1.weight'), W, M, W, 4 * W, dxn, W, epi=none, b_kmajor=1, to=g)
         g.add('mdt_ln_modulate_bwd_f32', dxn.data_ptr(), xmid.data_ptr(), sc2, NM, rows, dxp, 1, dsh2, dsc2, NM, stats.data_ptr(), M, W)
         # --- attention branch: x_mid = x_in + g1 * proj(attn(qkv(xn1)))
         g.add('mdt_gate_bwd_f32', dxp, fa.data_ptr(), g1, NM, rows, df.data_ptr(), dg1, NM, M, W)
-        self._tn32(df, W, ao, W, M, W, W, Gn('attn.proj.weight'), W)
-        self._cs32(df, W, Gn('attn.proj.bias'), M, W)
-        self._g32(df, W, Pf('attn.proj.weight'), W, M, W, W, dao, W, epi=none, b_kmajor=1, to=g)
+        self._tn32(df, W, ao, W, M, W, W, Gf(p + 'attn.proj.weight'), W)
+        self._cs32(df, W, Gf(p + 'attn.proj.bias'), M, W)
+        self._g32(df, W, Pf(p + 'attn.proj.weight'), W, M, W, W, dao, W, epi=none, b_kmajor=1, to=g)
         g.add('mdt_attn_f32_bwd', qkv.data_ptr(), dao.data_ptr(), ws['at'][0], ws['at'][1], dqkv.data_ptr(), B, rows, heads, hd)
         g.add('mdt_ln_modulate_f32', x_in.data_ptr(), sh1, sc1, NM, rows, xn.data_ptr(), M, W)
-        self._tn32(dqkv, 3 * W, xn, W, M, 3 * W, W, Gn('attn.qkv.weight'), W)
-        self._cs32(dqkv, 3 * W, Gn('attn.qkv.bias'), M, 3 * W)
-        self._g32(dqkv, 3 * W, Pf('attn.qkv.weight'), W, M, W, 3 * W, dxn, W, epi=none, b_kmajor=1, to=g)
+        self._tn32(dqkv, 3 * W, xn, W, M, 3 * W, W, Gf(p + 'attn.qkv.weight'), W)
+        self._cs32(dqkv, 3 * W, Gf(p + 'attn.qkv.bias'), M, 3 * W)
+        self._g32(dqkv, 3 * W, Pf(p + 'attn.qkv.weight'), W, M, W, 3 * W, dxn, W, epi=none, b_kmajor=1, to=g)
         g.add('mdt_ln_modulate_bwd_f32', dxn.data_ptr(), x_in.data_ptr(), sc1, NM, rows, dxp, 1, dsh1, dsc1, NM, stats.data_ptr(), M, W)
 
     def _g32(self, A, lda, Bw, ldb, M, N, K, out, ldo, bias=0, epi=F32EPI_NONE, res=None, ldres=0, gate=0, gate_ld=0, rps=1,
@@ -1068,39 +1009,62 @@ class PassPlan:
         x3 = self.precision == 'bf16x3' and batch <= 1 and not b_kmajor
         (to or self.fwd).add('mdt_gemm_bf16x3' if x3 else 'mdt_gemm_f32', C.byref(self._k(a)))
 
-    def _block_fwd_f32(self, prefix, tag, i, x_in, mod, moff, W, heads, rows, M):
-        """DiTBlock.forward (models/maskdit.py:188-192) in fp32; all blocks of a stack share one buffer set."""
-        eng, lay, f = self.eng, self.eng.lay, self.fwd
-        NM = eng.sp.n_mod
+    def _block_fwd_f32(self, prefix, tag, i, x_in, mod, moff, W, heads, rows, M, save):
+        """DiTBlock.forward (models/maskdit.py:188-192) in fp32.  Inference (`save` False): all blocks of a stack share one
+        buffer set, GELU and gate + residual are GEMM epilogues.  `save`: the block keeps qkv, the attention output, both
+        branch outputs f, x_mid and the pre-GELU h for its backward."""
+        f, Pf, p = self.fwd, self.Pf, prefix + '.'
+        NM = self.eng.sp.n_mod
         hd = W // heads
         B = self.B
-        Pp = eng.P.data_ptr()
-        Pf = lambda n: Pp + 4 * lay.off[f'{prefix}.{n}']  # noqa: E731
+        s = f'{tag}{i}' if save else tag
         mp = mod.data_ptr()
         sh1, sc1, g1, sh2, sc2, g2 = (mp + 4 * (moff + k * W) for k in range(6))
-        xn = self.f32(f'xn_{tag}', M, W)
-        qkv = self.f32(f'qkv_{tag}', M, 3 * W)
-        ws_floats = int(_lib.lib().mdt_attn_f32_ws_floats(B, rows, heads, hd))  # 0: the fused single-launch kernel serves this shape
-        S = self.f32(f'scores_{tag}', ws_floats) if ws_floats else None
-        ao = self.f32(f'ao_{tag}', M, W)
-        xmid = self.f32(f'xmid_{tag}', M, W)
-        h = self.f32(f'h_{tag}', M, 4 * W)
-        xout = self.f32(f'x_{tag}pp{(i + 1) % 2}', M, W)
+        xn = self.f32(f'xn_{tag}', M, W)  # (shared by the stack in either plan: the backward recomputes it)
+        qkv, ao = self.f32(f'qkv_{s}', M, 3 * W), self.f32(f'ao_{s}', M, W)
+        xmid, h = self.f32(f'xmid_{s}', M, W), self.f32(f'h_{s}', M, 4 * W)
+        xout = self.f32(f'x_{tag}{i + 1}' if save else f'x_{tag}pp{(i + 1) % 2}', M, W)
+        S = None  # attention scores; no workspace where the fused single-launch kernel serves the shape
+        ws_floats = int(_lib.lib().mdt_attn_f32_ws_floats(B, rows, heads, hd))
+        if ws_floats:  # (the backward's score workspace is at least twice as large)
+            S = self._f32ws['at'][0] if save else self.f32(f'scores_{tag}', ws_floats).data_ptr()
+
+        def branch(a, K, wname, res, gate, y, out):
+            """out = res + gate * Linear(a): in the GEMM's epilogue, or (save) y = Linear(a) kept and the rest a pass"""
+            if save:
+                self._g32(a, K, Pf(p + wname + '.weight'), K, M, W, K, self.f32(y, M, W), W, bias=Pf(p + wname + '.bias'))
+                f.add('mdt_gate_res_f32', res.data_ptr(), self.buf[y].data_ptr(), gate, NM, rows, out.data_ptr(), M, W)
+            else:
+                self._g32(a, K, Pf(p + wname + '.weight'), K, M, W, K, out, W, bias=Pf(p + wname + '.bias'), epi=F32EPI_GATE_RES,
+                          res=res, ldres=W, gate=gate, gate_ld=NM, rps=rows)
+
         f.add('mdt_ln_modulate_f32', x_in.data_ptr(), sh1, sc1, NM, rows, xn.data_ptr(), M, W)
-        self._g32(xn, W, Pf('attn.qkv.weight'), W, M, 3 * W, W, qkv, 3 * W, bias=Pf('attn.qkv.bias'))
+        self._g32(xn, W, Pf(p + 'attn.qkv.weight'), W, M, 3 * W, W, qkv, 3 * W, bias=Pf(p + 'attn.qkv.bias'))
         # timm Attention: softmax(q k^T * hd^-0.5) v per (sample, head) on the packed [M, (3, heads, hd)] buffer
-        f.add('mdt_attn_f32', qkv.data_ptr(), ao.data_ptr(), S.data_ptr() if S is not None else None, B, rows, heads, hd)
-        self._g32(ao, W, Pf('attn.proj.weight'), W, M, W, W, xmid, W, bias=Pf('attn.proj.bias'), epi=F32EPI_GATE_RES,
-                  res=x_in, ldres=W, gate=g1, gate_ld=NM, rps=rows)
+        f.add('mdt_attn_f32', qkv.data_ptr(), ao.data_ptr(), S, B, rows, heads, hd)
+        branch(ao, W, 'attn.proj', x_in, g1, f'fa_{s}', xmid)
         f.add('mdt_ln_modulate_f32', xmid.data_ptr(), sh2, sc2, NM, rows, xn.data_ptr(), M, W)
-        self._g32(xn, W, Pf('mlp.fc1.weight'), W, M, 4 * W, W, h, 4 * W, bias=Pf('mlp.fc1.bias'), epi=F32EPI_GELU)
-        self._g32(h, 4 * W, Pf('mlp.fc2.weight'), 4 * W, M, W, 4 * W, xout, W, bias=Pf('mlp.fc2.bias'), epi=F32EPI_GATE_RES,
-                  res=xmid, ldres=W, gate=g2, gate_ld=NM, rps=rows)
+        self._g32(xn, W, Pf(p + 'mlp.fc1.weight'), W, M, 4 * W, W, h, 4 * W, bias=Pf(p + 'mlp.fc1.bias'),
+                  epi=F32EPI_NONE if save else F32EPI_GELU)
+        act = h
+        if save:  # (shared by the stack: the backward recomputes it from h)
+            act = self.f32(f'act_{tag}', M, 4 * W)
+            f.add('mdt_gelu_f32', h.data_ptr(), act.data_ptr(), M * 4 * W)
+        branch(act, 4 * W, 'mlp.fc2', xmid, g2, f'fm_{s}', xout)
         return xout
 
     def _k(self, obj):
+        """Every ctypes struct a launch refers to stays alive as long as the plan."""
         self.fwd.keep.append(obj)
         return obj
+
+    def _nt16(self, to: Plan, *a, **kw):
+        """One mdt_gemm_nt launch appended to `to` (arguments: _nt)."""
+        to.add('mdt_gemm_nt', C.byref(self._k(_nt(*a, **kw))))
+
+    def _tn16(self, to: Plan, *a, **kw):
+        """One mdt_gemm_tn launch appended to `to` (arguments: _tn)."""
+        to.add('mdt_gemm_tn', C.byref(self._k(_tn(*a, **kw))))
 
     def _slab(self, name):
         ref = self._eng_ref
@@ -1113,19 +1077,16 @@ class PassPlan:
 
         self.bwd.add_callback(cb)
 
-    # ---- one DiT block ---------------------------------------------------------------------
     def _block_fwd(self, prefix, tag, i, x_in, mod, moff, W, heads, rows, M, lvalid=0, pending=None, defer_out=False):
         """DiTBlock.forward (models/maskdit.py:188-192) as 7 launches.  `pending` = (xres, y, gate) of the previous block's
         MLP branch: this block's first LayerNorm pass then forms x_in = xres + gate * y itself (FUSE_RES_LN); `defer_out`
         hands this block's own MLP residual to whoever normalises its output next.  Returns (x_out buffer, pending)."""
-        eng, lay, f = self.eng, self.eng.lay, self.fwd
-        NM = eng.sp.n_mod
+        f = self.fwd
+        NM = self.eng.sp.n_mod
         hd = W // heads
         B = self.B
         s = f'{tag}{i}' if self.train else f'{tag}'  # eval: all blocks share one buffer set
-        Pp, W16p = eng.P.data_ptr(), eng.W16.data_ptr()
-        Pf = lambda n: Pp + 4 * lay.off[f'{prefix}.{n}']  # noqa: E731
-        Wp = lambda n: W16p + 2 * lay.off[f'{prefix}.{n}']  # noqa: E731
+        p, Pf, Wp = prefix + '.', self.Pf, self.Wp
         mp = mod.data_ptr()
         sh1, sc1, g1, sh2, sc2, g2 = (mp + 4 * (moff + k * W) for k in range(6))
         xn1, st1 = self.b16(f'xn1_{s}', M, W), self.f32(f'st1_{s}', M, 2)
@@ -1147,54 +1108,52 @@ class PassPlan:
                   x_in.data_ptr(), xn1.data_ptr(), st1.data_ptr(), M, W)
         else:
             f.add('mdt_ln_modulate_fwd', x_in.data_ptr(), sh1, sc1, NM, rows, xn1.data_ptr(), st1.data_ptr(), M, W)
-        f.add('mdt_gemm_nt', C.byref(self._k(_nt(xn1.data_ptr(), W, Wp('attn.qkv.weight'), W, M, 3 * W, W, bias=Pf('attn.qkv.bias'),
-                                               epi=EPI_BF16, out=qkv.data_ptr(), ldo=3 * W))))
+        self._nt16(f, xn1.data_ptr(), W, Wp(p + 'attn.qkv.weight'), W, M, 3 * W, W, bias=Pf(p + 'attn.qkv.bias'), epi=EPI_BF16,
+                   out=qkv.data_ptr(), ldo=3 * W)
         f.add('mdt_attn_fwd', qkv.data_ptr(), ao.data_ptr(), lse.data_ptr(), B, rows, heads, hd, lvalid)
         # the bf16 copies of the branch outputs (ya, ym) and the pre-activation h are saved for the
         # backward only: inference plans skip those stores (2 of 10 resp. 2 of 4 epilogue bytes / element)
         if fuse:  # the GEMM stores y only; x_mid = x_in + g1 * y is formed by the LayerNorm pass that consumes it
-            f.add('mdt_gemm_nt', C.byref(self._k(_nt(ao.data_ptr(), W, Wp('attn.proj.weight'), W, M, W, W, bias=Pf('attn.proj.bias'),
-                                                   epi=EPI_BF16, out=ya.data_ptr(), ldo=W))))
+            self._nt16(f, ao.data_ptr(), W, Wp(p + 'attn.proj.weight'), W, M, W, W, bias=Pf(p + 'attn.proj.bias'), epi=EPI_BF16,
+                       out=ya.data_ptr(), ldo=W)
             f.add('mdt_ln_modulate_fwd_res', x_in.data_ptr(), ya.data_ptr(), g1, NM, sh2, sc2, NM, rows, xmid.data_ptr(),
                   xn2.data_ptr(), st2.data_ptr(), M, W)
         else:
-            f.add('mdt_gemm_nt', C.byref(self._k(_nt(ao.data_ptr(), W, Wp('attn.proj.weight'), W, M, W, W, bias=Pf('attn.proj.bias'),
-                                                   epi=EPI_GATE_RES, out=ya.data_ptr() if tr else 0, ldo=W, outf=xmid.data_ptr(), ldof=W,
-                                                   res=x_in.data_ptr(), ldres=W, gate=g1, gate_ld=NM, rps=rows))))
+            self._nt16(f, ao.data_ptr(), W, Wp(p + 'attn.proj.weight'), W, M, W, W, bias=Pf(p + 'attn.proj.bias'), epi=EPI_GATE_RES,
+                       out=ya.data_ptr() if tr else 0, ldo=W, outf=xmid.data_ptr(), ldof=W, res=x_in.data_ptr(), ldres=W,
+                       gate=g1, gate_ld=NM, rps=rows)
             f.add('mdt_ln_modulate_fwd', xmid.data_ptr(), sh2, sc2, NM, rows, xn2.data_ptr(), st2.data_ptr(), M, W)
-        f.add('mdt_gemm_nt', C.byref(self._k(_nt(xn2.data_ptr(), W, Wp('mlp.fc1.weight'), W, M, 4 * W, W, bias=Pf('mlp.fc1.bias'),
-                                               epi=EPI_GELU, out=h.data_ptr() if tr else 0, ldo=4 * W, out2=a.data_ptr(), ldo2=4 * W))))
+        self._nt16(f, xn2.data_ptr(), W, Wp(p + 'mlp.fc1.weight'), W, M, 4 * W, W, bias=Pf(p + 'mlp.fc1.bias'), epi=EPI_GELU,
+                   out=h.data_ptr() if tr else 0, ldo=4 * W, out2=a.data_ptr(), ldo2=4 * W)
         if fuse and defer_out:
-            f.add('mdt_gemm_nt', C.byref(self._k(_nt(a.data_ptr(), 4 * W, Wp('mlp.fc2.weight'), 4 * W, M, W, 4 * W, bias=Pf('mlp.fc2.bias'),
-                                                   epi=EPI_BF16, out=ym.data_ptr(), ldo=W))))
+            self._nt16(f, a.data_ptr(), 4 * W, Wp(p + 'mlp.fc2.weight'), 4 * W, M, W, 4 * W, bias=Pf(p + 'mlp.fc2.bias'), epi=EPI_BF16,
+                       out=ym.data_ptr(), ldo=W)
             return xout, (xmid, ym, g2)
-        f.add('mdt_gemm_nt', C.byref(self._k(_nt(a.data_ptr(), 4 * W, Wp('mlp.fc2.weight'), 4 * W, M, W, 4 * W, bias=Pf('mlp.fc2.bias'),
-                                               epi=EPI_GATE_RES, out=ym.data_ptr() if tr else 0, ldo=W, outf=xout.data_ptr(), ldof=W,
-                                               res=xmid.data_ptr(), ldres=W, gate=g2, gate_ld=NM, rps=rows))))
+        self._nt16(f, a.data_ptr(), 4 * W, Wp(p + 'mlp.fc2.weight'), 4 * W, M, W, 4 * W, bias=Pf(p + 'mlp.fc2.bias'), epi=EPI_GATE_RES,
+                   out=ym.data_ptr() if tr else 0, ldo=W, outf=xout.data_ptr(), ldof=W, res=xmid.data_ptr(), ldres=W,
+                   gate=g2, gate_ld=NM, rps=rows)
         return xout, None
 
-    def _gate_info(self, prefix, tag, i, mod, dmod, moff, W, Gf):
+    def _gate_info(self, prefix, tag, i, mod, dmod, moff, W):
         """Trailing arguments of mdt_ln_modulate_bwd_gate for the MLP residual gate of block (tag, i):
         (y = fc2 output, gate, gate_ld, dys, dgate, dgate_ld, dbias)."""
         NM = self.eng.sp.n_mod
         ym = self.buf[f'ym_{tag}{i}']
         return (ym.data_ptr(), mod.data_ptr() + 4 * (moff + 5 * W), NM, self._ws['dys'].data_ptr(),
-                dmod.data_ptr() + 4 * (moff + 5 * W), NM, Gf(f'{prefix}.mlp.fc2.bias'))
+                dmod.data_ptr() + 4 * (moff + 5 * W), NM, self.Gf(f'{prefix}.mlp.fc2.bias'))
 
-    def _block_bwd(self, prefix, tag, i, x_in, mod, dmod, moff, W, heads, rows, M, dx, Gf, fuse_next=None, skip_first_gate=False,
+    def _block_bwd(self, prefix, tag, i, x_in, mod, dmod, moff, W, heads, rows, M, dx, fuse_next=None, skip_first_gate=False,
                    lvalid=0):
         """Backward of DiTBlock: dx (fp32 residual-stream gradient) is updated in place.  The gate
         backward that opens the block is folded into the LayerNorm backward that precedes it in stream
         order (`skip_first_gate`), and the block's last LayerNorm backward carries the next block's
         (`fuse_next`)."""
-        eng, lay, g, ws = self.eng, self.eng.lay, self.bwd, self._ws
-        NM = eng.sp.n_mod
+        g, ws = self.bwd, self._ws
+        NM = self.eng.sp.n_mod
         hd = W // heads
         B = self.B
         s = f'{tag}{i}'
-        W16p, WTp = eng.W16.data_ptr(), eng.WT16.data_ptr()
-        WT = lambda n: WTp + 2 * lay.t_off[f'{prefix}.{n}']  # noqa: E731
-        Gn = lambda n: Gf(f'{prefix}.{n}')  # noqa: E731
+        p, WT, Gf = prefix + '.', self.WT, self.Gf
         mp, dp = mod.data_ptr(), dmod.data_ptr()
         sc1, g1, sc2, g2 = mp + 4 * (moff + W), mp + 4 * (moff + 2 * W), mp + 4 * (moff + 4 * W), mp + 4 * (moff + 5 * W)
         dsh1, dsc1, dg1, dsh2, dsc2, dg2 = (dp + 4 * (moff + k * W) for k in range(6))
@@ -1203,35 +1162,34 @@ class PassPlan:
         ya, xmid, xn2, st2, h, a, ym = b[f'ya_{s}'], b[f'xmid_{s}'], b[f'xn2_{s}'], b[f'st2_{s}'], b[f'h_{s}'], b[f'a_{s}'], b[f'ym_{s}']
         dys, dh, dxn, dao, dqkv, delta = (ws[k].data_ptr() for k in ('dys', 'dh', 'dxn', 'dao', 'dqkv', 'delta'))
         dxp = dx.data_ptr()
-        K = self._k
         # --- MLP branch: x_out = x_mid + g2 * (fc2(gelu(fc1(xn2))))
         if not skip_first_gate:
-            g.add('mdt_gate_bwd', dxp, ym.data_ptr(), g2, NM, rows, dys, dg2, NM, Gn('mlp.fc2.bias'), M, W)
-        g.add('mdt_gemm_tn', C.byref(K(_tn(dys, W, a.data_ptr(), 4 * W, M, W, 4 * W, Gn('mlp.fc2.weight'), 4 * W))))
+            g.add('mdt_gate_bwd', dxp, ym.data_ptr(), g2, NM, rows, dys, dg2, NM, Gf(p + 'mlp.fc2.bias'), M, W)
+        self._tn16(g, dys, W, a.data_ptr(), 4 * W, M, W, 4 * W, Gf(p + 'mlp.fc2.weight'), 4 * W)
         # dh = (dys W2) * gelu'(h); its column sums (= d fc1.bias) come out of the same epilogue
-        g.add('mdt_gemm_nt', C.byref(K(_nt(dys, W, WT('mlp.fc2.weight'), W, M, 4 * W, W, epi=EPI_DGELU, out=dh, ldo=4 * W,
-                                         aux=h.data_ptr(), ldaux=4 * W, colsum=Gn('mlp.fc1.bias') if FUSE_COLSUM else 0))))
-        g.add('mdt_gemm_tn', C.byref(K(_tn(dh, 4 * W, xn2.data_ptr(), W, M, 4 * W, W, Gn('mlp.fc1.weight'), W))))
+        self._nt16(g, dys, W, WT(p + 'mlp.fc2.weight'), W, M, 4 * W, W, epi=EPI_DGELU, out=dh, ldo=4 * W, aux=h.data_ptr(),
+                   ldaux=4 * W, colsum=Gf(p + 'mlp.fc1.bias') if FUSE_COLSUM else 0)
+        self._tn16(g, dh, 4 * W, xn2.data_ptr(), W, M, 4 * W, W, Gf(p + 'mlp.fc1.weight'), W)
         if not FUSE_COLSUM:
-            g.add('mdt_colsum_bf16', dh, 4 * W, Gn('mlp.fc1.bias'), M, 4 * W)
-        g.add('mdt_gemm_nt', C.byref(K(_nt(dh, 4 * W, WT('mlp.fc1.weight'), 4 * W, M, W, 4 * W, epi=EPI_BF16, out=dxn, ldo=W))))
+            g.add('mdt_colsum_bf16', dh, 4 * W, Gf(p + 'mlp.fc1.bias'), M, 4 * W)
+        self._nt16(g, dh, 4 * W, WT(p + 'mlp.fc1.weight'), 4 * W, M, W, 4 * W, epi=EPI_BF16, out=dxn, ldo=W)
         # --- attention branch: x_mid = x_in + g1 * proj(attn(qkv(xn1)))
         if FUSE_LN_GATE:  # the gate backward rides on LN2's backward
             g.add('mdt_ln_modulate_bwd_gate', dxn, xmid.data_ptr(), st2.data_ptr(), sc2, NM, rows, dxp, 1, dsh2, dsc2, NM, M, W,
-                  ya.data_ptr(), g1, NM, dys, dg1, NM, Gn('attn.proj.bias'))
+                  ya.data_ptr(), g1, NM, dys, dg1, NM, Gf(p + 'attn.proj.bias'))
         else:
             g.add('mdt_ln_modulate_bwd', dxn, xmid.data_ptr(), st2.data_ptr(), sc2, NM, rows, dxp, 1, dsh2, dsc2, NM, M, W)
-            g.add('mdt_gate_bwd', dxp, ya.data_ptr(), g1, NM, rows, dys, dg1, NM, Gn('attn.proj.bias'), M, W)
-        g.add('mdt_gemm_tn', C.byref(K(_tn(dys, W, ao.data_ptr(), W, M, W, W, Gn('attn.proj.weight'), W))))
-        g.add('mdt_gemm_nt', C.byref(K(_nt(dys, W, WT('attn.proj.weight'), W, M, W, W, epi=EPI_BF16, out=dao, ldo=W))))
+            g.add('mdt_gate_bwd', dxp, ya.data_ptr(), g1, NM, rows, dys, dg1, NM, Gf(p + 'attn.proj.bias'), M, W)
+        self._tn16(g, dys, W, ao.data_ptr(), W, M, W, W, Gf(p + 'attn.proj.weight'), W)
+        self._nt16(g, dys, W, WT(p + 'attn.proj.weight'), W, M, W, W, epi=EPI_BF16, out=dao, ldo=W)
         g.add('mdt_attn_bwd', qkv.data_ptr(), ao.data_ptr(), dao, lse.data_ptr(), delta, dqkv, B, rows, heads, hd, lvalid)
         # the qkv bias gradient (column sums of dqkv) comes out of the weight-gradient GEMM, which streams dqkv through
         # LDS anyway (mdt_gemm_tn_args.colsum_a): one pass over dqkv less per block
-        g.add('mdt_gemm_tn', C.byref(K(_tn(dqkv, 3 * W, xn1.data_ptr(), W, M, 3 * W, W, Gn('attn.qkv.weight'), W,
-                                          colsum_a=Gn('attn.qkv.bias') if FUSE_QKV_COLSUM else 0))))
+        self._tn16(g, dqkv, 3 * W, xn1.data_ptr(), W, M, 3 * W, W, Gf(p + 'attn.qkv.weight'), W,
+                   colsum_a=Gf(p + 'attn.qkv.bias') if FUSE_QKV_COLSUM else 0)
         if not FUSE_QKV_COLSUM:
-            g.add('mdt_colsum_bf16', dqkv, 3 * W, Gn('attn.qkv.bias'), M, 3 * W)
-        g.add('mdt_gemm_nt', C.byref(K(_nt(dqkv, 3 * W, WT('attn.qkv.weight'), 3 * W, M, W, 3 * W, epi=EPI_BF16, out=dxn, ldo=W))))
+            g.add('mdt_colsum_bf16', dqkv, 3 * W, Gf(p + 'attn.qkv.bias'), M, 3 * W)
+        self._nt16(g, dqkv, 3 * W, WT(p + 'attn.qkv.weight'), 3 * W, M, W, 3 * W, epi=EPI_BF16, out=dxn, ldo=W)
         if fuse_next is not None:
             g.add('mdt_ln_modulate_bwd_gate', dxn, x_in.data_ptr(), st1.data_ptr(), sc1, NM, rows, dxp, 1, dsh1, dsc1, NM, M, W,
                   *fuse_next)
@@ -1240,6 +1198,7 @@ class PassPlan:
 
     # ---- execution ---------------------------------------------------------------------------
     def run_forward(self) -> int:
+        self.eng._refuse_listing('PassPlan.run_forward')  # (before torch.cuda is asked for a stream)
         if self.eng.shadows_dirty and not reads_f32_arena(self.precision):  # (an fp32 / bf16x3 plan reads the master arena itself)
             self.eng.refresh_shadows()
         self.gen += 1
@@ -1255,4 +1214,5 @@ class PassPlan:
                 'maskdit_amd: backward of a forward whose saved activations were overwritten by a later forward of the '
                 f'same shape (forward #{gen}, buffers now hold #{self.gen}).  Call backward() before the next forward '
                 '(gradient accumulation: one forward/backward per micro-batch), or evaluate under torch.no_grad().')
+        self.eng._refuse_listing('PassPlan.run_backward')
         self.bwd.run(torch.cuda.current_stream().cuda_stream)
