@@ -205,6 +205,26 @@ int mdt_final_bwd(const float* dF, const float* x, const float* stats, const flo
                   float* dshift, float* dscale, int dmod_ld, int B, int T, int Dd, int C, int p,
                   mdt_stream_t stream);
 
+/* FinalLayer + unpatchify of a decoder-less model (use_decoder=False, models/maskdit.py:529-553): the final layer
+ * reads the encoder's rows.  x f32 [B*L_pitch, D] (L_pitch = 0 means L), of which rows r < L of every sample are real
+ * (the kept tokens; L is a run-time count, L_pitch the plan's 64-row pitch); stats [B*L_pitch, 2], written / read at
+ * the real rows only.  ids = the [B, 2T] int32 table of mdt_mask_sort (shuffle | restore), row pitch ids_ld; NULL =
+ * identity with L == T.  The forward reads the RESTORE half (one wave per image token j: r = restore[b][j]; r < L
+ * computes row r, r >= L stores zeros), so every patch of F [B,C,R,R] is written exactly once -- kept tokens at their
+ * image position, removed patches exactly 0.0f -- whatever F held before, and padding rows of x are never read.  The
+ * backward reads the SHUFFLE half (one wave per row r: token shuffle[b][r]); it reads dF at kept patches only, stores dx
+ * for the real rows and exact zeros for rows L <= r < L_pitch, and ADDS into dW [p*p*C, D], dbias, dshift[b] and
+ * dscale[b] (two launches: dx + modulation + bias, then dW).
+ * Domain: D <= 1280 and D % 4 == 0; T a square; p*p*C <= 16, or 64 / 256 with D % 32 == 0; x, shift, scale, W, dx
+ * 16-byte aligned and mod_ld % 4 == 0; 1 <= L <= T, L_pitch >= L.  Anything else is refused before any launch. */
+int mdt_final_keep_fwd(const float* x, const float* shift, const float* scale, int mod_ld, const float* W,
+                       const float* bias, const int32_t* ids, int ids_ld, float* F, float* stats, int B, int T, int L,
+                       int L_pitch, int D, int C, int p, mdt_stream_t stream);
+int mdt_final_keep_bwd(const float* dF, const float* x, const float* stats, const float* shift, const float* scale,
+                       int mod_ld, const float* W, const int32_t* ids, int ids_ld, float* dx, float* dW, float* dbias,
+                       float* dshift, float* dscale, int dmod_ld, int B, int T, int L, int L_pitch, int D, int C, int p,
+                       mdt_stream_t stream);
+
 /* ---------------------------------------------------------------- EDM precond / loss ---- */
 
 /* EDMLoss noise draw + EDMPrecond coefficients (train_utils/loss.py:35-39,

@@ -77,6 +77,8 @@ _PROTOS = {
     'mdt_unmask_bwd': [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32],
     'mdt_final_fwd': [vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32],
     'mdt_final_bwd': [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32],
+    'mdt_final_keep_fwd': [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32],
+    'mdt_final_keep_bwd': [vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32],
     'mdt_edm_prep': [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32],
     'mdt_edm_loss_fwd': [vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32],
     'mdt_edm_loss_bwd': [vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, i32],

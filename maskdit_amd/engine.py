@@ -79,6 +79,10 @@ class Spec:
     Dd: int = DEC_HIDDEN
     ddepth: int = DEC_DEPTH
     dheads: int = DEC_HEADS
+    # use_decoder=False (models/maskdit.py:308-331, 529-553): no DecoderLayer, decoder blocks, decoder_pos_embed or mask
+    # token; the final layer reads the encoder's rows at width D.  Such a spec carries ddepth = 0 and Dd = D, so that
+    # "the final layer's width" stays sp.Dd for both kinds.
+    use_decoder: bool = True
 
     @property
     def T(self):
@@ -98,6 +102,8 @@ class Spec:
 
     @property
     def n_mod(self):
+        if not self.use_decoder:
+            return self.depth * 6 * self.D + 2 * self.D
         return self.depth * 6 * self.D + self.ddepth * 6 * self.Dd + 2 * self.D + 2 * self.Dd
 
     def mod_off(self, kind, i=0):
@@ -105,6 +111,10 @@ class Spec:
         if kind == 'enc':
             return i * 6 * self.D
         base = self.depth * 6 * self.D
+        if not self.use_decoder:
+            if kind != 'fin':
+                raise KeyError(f'a decoder-less model has no {kind!r} modulation rows')
+            return base
         if kind == 'dec':
             return base + i * 6 * self.Dd
         base += self.ddepth * 6 * self.Dd
@@ -116,10 +126,11 @@ class Spec:
 def make_spec(model_type, img_resolution, img_channels, num_classes, use_decoder=True, mae_loss_coef=0.1):
     if model_type not in MODEL_CONFIGS:
         raise ValueError(f'unknown model_type {model_type}')
-    if not use_decoder:
-        raise NotImplementedError('maskdit_amd accelerates the shipped configuration (use_decoder=True) only')
     depth, D, p, heads = MODEL_CONFIGS[model_type]
     sp = Spec(model_type, depth, D, heads, p, img_resolution, img_channels, num_classes, mae_loss_coef > 0)
+    if not use_decoder:
+        sp = Spec(model_type, depth, D, heads, p, img_resolution, img_channels, num_classes, mae_loss_coef > 0,
+                  Dd=D, ddepth=0, dheads=heads, use_decoder=False)
     if sp.hd not in (32, 64, 72, 80):
         raise NotImplementedError(f'head_dim {sp.hd} unsupported')
     # the token-boundary kernels serve patch vectors of 16 elements (embed.hip / loss.hip) and of 64 and 256 (patch.hip)
@@ -158,15 +169,17 @@ def param_table(sp: Spec) -> List[Tuple[str, tuple]]:
     for i in range(sp.ddepth):
         ada(f'model.decoder_blocks.{i}', 6 * Dd)
         block(f'model.decoder_blocks.{i}', Dd)
-    ada('model.decoder_layer', 2 * D)
+    if sp.use_decoder:
+        ada('model.decoder_layer', 2 * D)
     ada('model.final_layer', 2 * Dd)
-    rest.extend([('model.decoder_layer.linear.weight', (Dd, D)), ('model.decoder_layer.linear.bias', (Dd,)),
-                 ('model.final_layer.linear.weight', (sp.pp, Dd)), ('model.final_layer.linear.bias', (sp.pp,)),
+    if sp.use_decoder:
+        rest.extend([('model.decoder_layer.linear.weight', (Dd, D)), ('model.decoder_layer.linear.bias', (Dd,))])
+    rest.extend([('model.final_layer.linear.weight', (sp.pp, Dd)), ('model.final_layer.linear.bias', (sp.pp,)),
                  ('model.x_embedder.proj.weight', (D, sp.C, sp.patch, sp.patch)), ('model.x_embedder.proj.bias', (D,)),
                  ('model.t_embedder.mlp.0.weight', (D, 256)), ('model.t_embedder.mlp.0.bias', (D,)),
                  ('model.t_embedder.mlp.2.weight', (D, D)), ('model.t_embedder.mlp.2.bias', (D,)),
                  ('model.y_embedder.embedding_table.weight', (D, sp.num_classes))])
-    if sp.mae:
+    if sp.mae and sp.use_decoder:  # (models/maskdit.py:323-324: the mask token belongs to the decoder)
         rest.append(('model.mask_token', (1, 1, Dd)))
     return ada_w + ada_b + rest
 
@@ -228,7 +241,8 @@ class Layout:
         for name, r0, r1 in self.ada_groups:
             self.slabs[name] = (self.ada_w + r0 * sp.D, self.ada_w + r1 * sp.D)
         self.slabs['ada_b'] = (self.ada_b, self.off['model.blocks.0.attn.qkv.weight'])
-        self.slabs['misc'] = (self.off['model.decoder_layer.linear.weight'], self.n)
+        self.slabs['misc'] = (self.off['model.decoder_layer.linear.weight' if sp.use_decoder else 'model.final_layer.linear.weight'],
+                              self.n)
 
 
 # ------------------------------------------------------------------------------------------
@@ -279,7 +293,7 @@ class Engine:
         self.WT16 = torch.zeros(self.lay.nt, device=dev, dtype=torch.bfloat16)
         self.Wy16 = torch.zeros(sp.D, YPAD, device=dev, dtype=torch.bfloat16)
         self.pos = torch.zeros(sp.T, sp.D, device=dev, dtype=torch.float32)
-        self.dpos = torch.zeros(sp.T, sp.Dd, device=dev, dtype=torch.float32)
+        self.dpos = torch.zeros(sp.T if sp.use_decoder else 0, sp.Dd, device=dev, dtype=torch.float32)  # decoder_pos_embed
         tab, tiles = [], 0
         for src, dst, rows, cols in self.lay.t_entries:
             tab += [src, dst, rows, cols, tiles]
@@ -339,6 +353,8 @@ class Engine:
         self._refuse_listing('Engine.plan')
         check_precision(precision)
         f32_train = precision == 'fp32' and train and not masked  # the unmasked stage (train.py --no_amp): _build_f32_train
+        if f32_train and not self.sp.use_decoder:
+            raise NotImplementedError(NODECODER_FP32_MESSAGE)
         if reads_f32_arena(precision) and (masked or train) and not f32_train:
             raise NotImplementedError('the fp32-faithful path covers inference (the sampler / eval forward: sample.py:56) and, at '
                                       "precision 'fp32', training of the UNMASKED stage (mask_ratio 0: train.py --no_amp); fp32 "
@@ -400,6 +416,10 @@ _PLAN_CLOCK = 0
 # (csrc/f32path.hip); 'bf16x3' = the fp32 plan with its Linear layers on mdt_gemm_bf16x3 (fp32-level accuracy on the bf16
 # matrix instruction), attention and everything else as in 'fp32'.
 PRECISIONS = ('bf16', 'fp32', 'bf16x3')
+
+
+NODECODER_FP32_MESSAGE = ("fp32 training (train precision 'fp32', train.py --no_amp) is not provided for a decoder-less model "
+                          "(use_decoder=False): it trains with the bf16 kernels (set_train_precision('bf16'), no --no_amp)")
 
 
 def check_precision(precision: str) -> str:
@@ -512,6 +532,8 @@ class PassPlan:
         if not reads_f32_arena(precision):
             self._build()
         elif train:  # (Engine.plan lets only the unmasked stage at 'fp32' through)
+            if not sp.use_decoder:
+                raise NotImplementedError(NODECODER_FP32_MESSAGE)
             self._build_f32_train()
         else:
             self._build_f32()
@@ -633,39 +655,52 @@ class PassPlan:
         pend = None  # (xres, y, gate address): the residual add the NEXT LayerNorm pass has to perform into xs_e[-1]
         for i in range(sp.depth):
             xo, pend = self._block_fwd(f'model.blocks.{i}', 'e', i, xs_e[-1], mod, sp.mod_off('enc', i), D, sp.heads, L, Me,
-                                       lvalid=self.lv_attn, pending=pend, defer_out=fuse)
+                                       lvalid=self.lv_attn, pending=pend,
+                                       defer_out=fuse and (sp.use_decoder or i + 1 < sp.depth))
             xs_e.append(xo)
-        # ---------------- decoder layer + unmask ----------------------------------------------
-        self.marks = {'enc_fwd_end': len(f.calls)}  # launch index where the encoder (+ conditioning path) forward ends
-        odl = sp.mod_off('dl')
-        xnd = self.b16('xn_dl', Me, D)
-        st_dl = self.f32('st_dl', Me, 2)
-        xdec = self.b16('xdec', Me, Dd)
-        if pend is not None:  # the top encoder block's MLP residual is formed here
-            f.add('mdt_ln_modulate_fwd_res', pend[0].data_ptr(), pend[1].data_ptr(), pend[2], NM, mod.data_ptr() + 4 * odl,
-                  mod.data_ptr() + 4 * (odl + D), NM, L, xs_e[-1].data_ptr(), xnd.data_ptr(), st_dl.data_ptr(), Me, D)
-            self.marks['enc_fwd_end'] = len(f.calls)  # (it is encoder work: the mark moves behind it)
+        if sp.use_decoder:
+            # ---------------- decoder layer + unmask ----------------------------------------------
+            self.marks = {'enc_fwd_end': len(f.calls)}  # launch index where the encoder (+ conditioning path) forward ends
+            odl = sp.mod_off('dl')
+            xnd = self.b16('xn_dl', Me, D)
+            st_dl = self.f32('st_dl', Me, 2)
+            xdec = self.b16('xdec', Me, Dd)
+            if pend is not None:  # the top encoder block's MLP residual is formed here
+                f.add('mdt_ln_modulate_fwd_res', pend[0].data_ptr(), pend[1].data_ptr(), pend[2], NM, mod.data_ptr() + 4 * odl,
+                      mod.data_ptr() + 4 * (odl + D), NM, L, xs_e[-1].data_ptr(), xnd.data_ptr(), st_dl.data_ptr(), Me, D)
+                self.marks['enc_fwd_end'] = len(f.calls)  # (it is encoder work: the mark moves behind it)
+            else:
+                f.add('mdt_ln_modulate_fwd', xs_e[-1].data_ptr(), mod.data_ptr() + 4 * odl, mod.data_ptr() + 4 * (odl + D), NM, L,
+                      xnd.data_ptr(), st_dl.data_ptr(), Me, D)
+            self._nt16(f, xnd.data_ptr(), D, Wp('model.decoder_layer.linear.weight'), D, Me, Dd, D,
+                       bias=Pf('model.decoder_layer.linear.bias'), epi=EPI_BF16, out=xdec.data_ptr(), ldo=Dd)
+            Md = B * T
+            xd0 = self.f32('x_d0', Md, Dd)
+            use_mt = self.masked and sp.mae
+            f.add('mdt_unmask_fwd', xdec.data_ptr(), (ids32.data_ptr() + 4 * T) if self.masked else None, 2 * T,
+                  Pf('model.mask_token') if use_mt else None, eng.dpos.data_ptr(), xd0.data_ptr(), B, T, self.lv_arg, Dd, L)
+            xs_d = [xd0]
+            pend = None
+            for i in range(sp.ddepth):  # (the last block forms its own output: mdt_final_fwd reads it)
+                xo, pend = self._block_fwd(f'model.decoder_blocks.{i}', 'd', i, xs_d[-1], mod, sp.mod_off('dec', i), Dd, sp.dheads, T, Md,
+                                           pending=pend, defer_out=fuse and i + 1 < sp.ddepth)
+                xs_d.append(xo)
+            ofin = sp.mod_off('fin')
+            st_f = self.f32('st_f', Md, 2)
+            f.add('mdt_final_fwd', xs_d[-1].data_ptr(), mod.data_ptr() + 4 * ofin, mod.data_ptr() + 4 * (ofin + Dd), NM,
+                  Pf('model.final_layer.linear.weight'), Pf('model.final_layer.linear.bias'), Fx.data_ptr(), st_f.data_ptr(),
+                  B, T, Dd, sp.C, sp.patch)
         else:
-            f.add('mdt_ln_modulate_fwd', xs_e[-1].data_ptr(), mod.data_ptr() + 4 * odl, mod.data_ptr() + 4 * (odl + D), NM, L,
-                  xnd.data_ptr(), st_dl.data_ptr(), Me, D)
-        self._nt16(f, xnd.data_ptr(), D, Wp('model.decoder_layer.linear.weight'), D, Me, Dd, D,
-                   bias=Pf('model.decoder_layer.linear.bias'), epi=EPI_BF16, out=xdec.data_ptr(), ldo=Dd)
-        Md = B * T
-        xd0 = self.f32('x_d0', Md, Dd)
-        use_mt = self.masked and sp.mae
-        f.add('mdt_unmask_fwd', xdec.data_ptr(), (ids32.data_ptr() + 4 * T) if self.masked else None, 2 * T,
-              Pf('model.mask_token') if use_mt else None, eng.dpos.data_ptr(), xd0.data_ptr(), B, T, self.lv_arg, Dd, L)
-        xs_d = [xd0]
-        pend = None
-        for i in range(sp.ddepth):  # (the last block forms its own output: mdt_final_fwd reads it)
-            xo, pend = self._block_fwd(f'model.decoder_blocks.{i}', 'd', i, xs_d[-1], mod, sp.mod_off('dec', i), Dd, sp.dheads, T, Md,
-                                       pending=pend, defer_out=fuse and i + 1 < sp.ddepth)
-            xs_d.append(xo)
-        ofin = sp.mod_off('fin')
-        st_f = self.f32('st_f', Md, 2)
-        f.add('mdt_final_fwd', xs_d[-1].data_ptr(), mod.data_ptr() + 4 * ofin, mod.data_ptr() + 4 * (ofin + Dd), NM,
-              Pf('model.final_layer.linear.weight'), Pf('model.final_layer.linear.bias'), Fx.data_ptr(), st_f.data_ptr(),
-              B, T, Dd, sp.C, sp.patch)
+            # ---------------- no decoder (models/maskdit.py:529-553): the final layer reads the encoder's rows; its kernel
+            # scatters the kept tokens' patches to their image positions and zeroes the removed ones -----------------------
+            self.marks = {'enc_fwd_end': len(f.calls)}
+            Md, xs_d = 0, []
+            ofin = sp.mod_off('fin')
+            st_f = self.f32('st_f', Me, 2)
+            ids_p = ids32.data_ptr() if ids32 is not None else None
+            f.add('mdt_final_keep_fwd', xs_e[-1].data_ptr(), mod.data_ptr() + 4 * ofin, mod.data_ptr() + 4 * (ofin + D), NM,
+                  Pf('model.final_layer.linear.weight'), Pf('model.final_layer.linear.bias'), ids_p, 2 * T, Fx.data_ptr(),
+                  st_f.data_ptr(), B, T, self.lv_arg, L, D, sp.C, sp.patch)
         if not train:
             return
         # =================== backward ===========================================================
@@ -674,37 +709,43 @@ class PassPlan:
         dmod = self.f32('dmod', Bp, NM)
         wmax = max(Me * D, Md * Dd)
         dxe = self.f32('dx_e', Me, D)
-        dxd = self.f32('dx_d', Md, Dd)
+        dxd = self.f32('dx_d', Md, Dd) if sp.use_decoder else None
         ws = dict(dys=self.b16('ws_dys', wmax), dh=self.b16('ws_dh', 4 * wmax), dxn=self.b16('ws_dxn', wmax),
                   dao=self.b16('ws_dao', wmax), dqkv=self.b16('ws_dqkv', 3 * wmax),
-                  delta=self.f32('ws_delta', max(B * sp.heads * L, B * sp.dheads * T)))
+                  delta=self.f32('ws_delta', max(B * sp.heads * L, B * sp.dheads * T if sp.use_decoder else 0)))
         self._ws = ws
         g.add_callback(lambda: dmod.zero_())
-        g.add('mdt_final_bwd', dF.data_ptr(), xs_d[-1].data_ptr(), st_f.data_ptr(), mod.data_ptr() + 4 * ofin,
-              mod.data_ptr() + 4 * (ofin + Dd), NM, Pf('model.final_layer.linear.weight'), dxd.data_ptr(),
-              Gf('model.final_layer.linear.weight'), Gf('model.final_layer.linear.bias'), dmod.data_ptr() + 4 * ofin,
-              dmod.data_ptr() + 4 * (ofin + Dd), NM, B, T, Dd, sp.C, sp.patch)
-        for i in reversed(range(sp.ddepth)):
-            # the LN1 backward that ends block i also runs the MLP-gate backward that would open block i-1
-            nxt = self._gate_info(f'model.decoder_blocks.{i - 1}', 'd', i - 1, mod, dmod, sp.mod_off('dec', i - 1), Dd) \
-                if (i > 0 and FUSE_LN_GATE) else None
-            self._block_bwd(f'model.decoder_blocks.{i}', 'd', i, xs_d[i], mod, dmod, sp.mod_off('dec', i), Dd, sp.dheads, T, Md,
-                            dxd, fuse_next=nxt, skip_first_gate=(FUSE_LN_GATE and i < sp.ddepth - 1))
-            self._slab(f'dec{i}')
-        dxdec = self.b16('dxdec', Me, Dd)
-        g.add('mdt_unmask_bwd', dxd.data_ptr(), ids32.data_ptr() if self.masked else None, 2 * T, dxdec.data_ptr(),
-              Gf('model.mask_token') if use_mt else None, B, T, self.lv_arg, Dd, L)
-        self._tn16(g, dxdec.data_ptr(), Dd, xnd.data_ptr(), D, Me, Dd, D, Gf('model.decoder_layer.linear.weight'), D)
-        g.add('mdt_colsum_bf16', dxdec.data_ptr(), Dd, Gf('model.decoder_layer.linear.bias'), Me, Dd)
-        self._nt16(g, dxdec.data_ptr(), Dd, WT('model.decoder_layer.linear.weight'), Dd, Me, D, Dd, epi=EPI_BF16,
-                   out=ws['dxn'].data_ptr(), ldo=D)
-        if FUSE_LN_GATE:
-            top = self._gate_info(f'model.blocks.{sp.depth - 1}', 'e', sp.depth - 1, mod, dmod, sp.mod_off('enc', sp.depth - 1), D)
-            g.add('mdt_ln_modulate_bwd_gate', ws['dxn'].data_ptr(), xs_e[-1].data_ptr(), st_dl.data_ptr(), mod.data_ptr() + 4 * (odl + D),
-                  NM, L, dxe.data_ptr(), 0, dmod.data_ptr() + 4 * odl, dmod.data_ptr() + 4 * (odl + D), NM, Me, D, *top)
+        if not sp.use_decoder:  # dx_e straight from the final layer: real rows stored, the pitch's padding rows zeroed
+            g.add('mdt_final_keep_bwd', dF.data_ptr(), xs_e[-1].data_ptr(), st_f.data_ptr(), mod.data_ptr() + 4 * ofin,
+                  mod.data_ptr() + 4 * (ofin + D), NM, Pf('model.final_layer.linear.weight'), ids_p, 2 * T, dxe.data_ptr(),
+                  Gf('model.final_layer.linear.weight'), Gf('model.final_layer.linear.bias'), dmod.data_ptr() + 4 * ofin,
+                  dmod.data_ptr() + 4 * (ofin + D), NM, B, T, self.lv_arg, L, D, sp.C, sp.patch)
         else:
-            g.add('mdt_ln_modulate_bwd', ws['dxn'].data_ptr(), xs_e[-1].data_ptr(), st_dl.data_ptr(), mod.data_ptr() + 4 * (odl + D),
-                  NM, L, dxe.data_ptr(), 0, dmod.data_ptr() + 4 * odl, dmod.data_ptr() + 4 * (odl + D), NM, Me, D)
+            g.add('mdt_final_bwd', dF.data_ptr(), xs_d[-1].data_ptr(), st_f.data_ptr(), mod.data_ptr() + 4 * ofin,
+                  mod.data_ptr() + 4 * (ofin + Dd), NM, Pf('model.final_layer.linear.weight'), dxd.data_ptr(),
+                  Gf('model.final_layer.linear.weight'), Gf('model.final_layer.linear.bias'), dmod.data_ptr() + 4 * ofin,
+                  dmod.data_ptr() + 4 * (ofin + Dd), NM, B, T, Dd, sp.C, sp.patch)
+            for i in reversed(range(sp.ddepth)):
+                # the LN1 backward that ends block i also runs the MLP-gate backward that would open block i-1
+                nxt = self._gate_info(f'model.decoder_blocks.{i - 1}', 'd', i - 1, mod, dmod, sp.mod_off('dec', i - 1), Dd) \
+                    if (i > 0 and FUSE_LN_GATE) else None
+                self._block_bwd(f'model.decoder_blocks.{i}', 'd', i, xs_d[i], mod, dmod, sp.mod_off('dec', i), Dd, sp.dheads, T, Md,
+                                dxd, fuse_next=nxt, skip_first_gate=(FUSE_LN_GATE and i < sp.ddepth - 1))
+                self._slab(f'dec{i}')
+            dxdec = self.b16('dxdec', Me, Dd)
+            g.add('mdt_unmask_bwd', dxd.data_ptr(), ids32.data_ptr() if self.masked else None, 2 * T, dxdec.data_ptr(),
+                  Gf('model.mask_token') if use_mt else None, B, T, self.lv_arg, Dd, L)
+            self._tn16(g, dxdec.data_ptr(), Dd, xnd.data_ptr(), D, Me, Dd, D, Gf('model.decoder_layer.linear.weight'), D)
+            g.add('mdt_colsum_bf16', dxdec.data_ptr(), Dd, Gf('model.decoder_layer.linear.bias'), Me, Dd)
+            self._nt16(g, dxdec.data_ptr(), Dd, WT('model.decoder_layer.linear.weight'), Dd, Me, D, Dd, epi=EPI_BF16,
+                       out=ws['dxn'].data_ptr(), ldo=D)
+            if FUSE_LN_GATE:
+                top = self._gate_info(f'model.blocks.{sp.depth - 1}', 'e', sp.depth - 1, mod, dmod, sp.mod_off('enc', sp.depth - 1), D)
+                g.add('mdt_ln_modulate_bwd_gate', ws['dxn'].data_ptr(), xs_e[-1].data_ptr(), st_dl.data_ptr(), mod.data_ptr() + 4 * (odl + D),
+                      NM, L, dxe.data_ptr(), 0, dmod.data_ptr() + 4 * odl, dmod.data_ptr() + 4 * (odl + D), NM, Me, D, *top)
+            else:
+                g.add('mdt_ln_modulate_bwd', ws['dxn'].data_ptr(), xs_e[-1].data_ptr(), st_dl.data_ptr(), mod.data_ptr() + 4 * (odl + D),
+                      NM, L, dxe.data_ptr(), 0, dmod.data_ptr() + 4 * odl, dmod.data_ptr() + 4 * (odl + D), NM, Me, D)
         dmod16 = self.b16('dmod16', Bp, NM)
 
         def ada_group(name, r0, r1):
@@ -716,13 +757,14 @@ class PassPlan:
             self._slab(name)
 
         groups = {name: (r0, r1) for name, r0, r1 in lay.ada_groups}
-        ada_group('ada_w_dec', *groups['ada_w_dec'])  # final layer, decoder blocks, decoder layer: all done above
+        ada_group('ada_w_dec', *groups['ada_w_dec'])  # final layer, decoder blocks, decoder layer: all done above (no decoder: the final layer's rows)
         self.marks['enc_bwd_begin'] = len(g.calls)  # everything from here on is encoder / conditioning-path backward
         for i in reversed(range(sp.depth)):
             nxt = self._gate_info(f'model.blocks.{i - 1}', 'e', i - 1, mod, dmod, sp.mod_off('enc', i - 1), D) \
                 if (i > 0 and FUSE_LN_GATE) else None
             self._block_bwd(f'model.blocks.{i}', 'e', i, xs_e[i], mod, dmod, sp.mod_off('enc', i), D, sp.heads, L, Me, dxe,
-                            fuse_next=nxt, skip_first_gate=FUSE_LN_GATE, lvalid=self.lv_attn)
+                            fuse_next=nxt, skip_first_gate=FUSE_LN_GATE and (sp.use_decoder or i + 1 < sp.depth),
+                            lvalid=self.lv_attn)
             self._slab(f'enc{i}')
             if f'ada_w_enc{i}' in groups:  # block i is the lowest block of its group
                 ada_group(f'ada_w_enc{i}', *groups[f'ada_w_enc{i}'])
@@ -800,6 +842,13 @@ class PassPlan:
         for i in range(sp.depth):
             xs_e.append(self._block_fwd_f32(f'model.blocks.{i}', 'e', i, xs_e[-1], mod, sp.mod_off('enc', i), D, sp.heads, T, M, save))
         self.marks = {'enc_fwd_end': len(f.calls)}
+        if not sp.use_decoder:  # (:529-553) the final layer reads the encoder's rows; every token is present
+            st_f = self.f32('st_f', M, 2)
+            ofin = sp.mod_off('fin')
+            f.add('mdt_final_keep_fwd', xs_e[-1].data_ptr(), mod.data_ptr() + 4 * ofin, mod.data_ptr() + 4 * (ofin + D), NM,
+                  Pf('model.final_layer.linear.weight'), Pf('model.final_layer.linear.bias'), None, 2 * T, Fx.data_ptr(),
+                  st_f.data_ptr(), B, T, T, T, D, sp.C, sp.patch)
+            return xs_e, []
         # ---------------- DecoderLayer (:195-213) + decoder_pos_embed (:545) -------------------------------------------
         odl = sp.mod_off('dl')
         xn_e, xdec = self.f32('xn_e', M, D), self.f32('xdec', M, Dd)

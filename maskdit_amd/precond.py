@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import call
-from .engine import MODEL_CONFIGS, Engine, Spec, check_precision, make_spec
+from .engine import MODEL_CONFIGS, NODECODER_FP32_MESSAGE, Engine, Spec, check_precision, make_spec
 
 
 TRAIN_PRECISIONS = ('bf16', 'fp32')
@@ -121,13 +121,15 @@ def reference_param_order(spec: Spec):
         return [f'{prefix}.{n}' for n in ('attn.qkv.weight', 'attn.qkv.bias', 'attn.proj.weight', 'attn.proj.bias',
                                           'mlp.fc1.weight', 'mlp.fc1.bias', 'mlp.fc2.weight', 'mlp.fc2.bias',
                                           'adaLN_modulation.1.weight', 'adaLN_modulation.1.bias')]
-    names = ['pos_embed', 'decoder_pos_embed'] + (['mask_token'] if spec.mae else [])
+    dec = spec.use_decoder  # (models/maskdit.py:302-331: without it decoder_pos_embed, mask_token, decoder_layer, decoder_blocks are None)
+    names = ['pos_embed'] + (['decoder_pos_embed'] + (['mask_token'] if spec.mae else []) if dec else [])
     names += ['x_embedder.proj.weight', 'x_embedder.proj.bias', 't_embedder.mlp.0.weight', 't_embedder.mlp.0.bias',
               't_embedder.mlp.2.weight', 't_embedder.mlp.2.bias', 'y_embedder.embedding_table.weight']
     for i in range(spec.depth):
         names += block(f'blocks.{i}')
-    names += ['decoder_layer.linear.weight', 'decoder_layer.linear.bias', 'decoder_layer.adaLN_modulation.1.weight',
-              'decoder_layer.adaLN_modulation.1.bias']
+    if dec:
+        names += ['decoder_layer.linear.weight', 'decoder_layer.linear.bias', 'decoder_layer.adaLN_modulation.1.weight',
+                  'decoder_layer.adaLN_modulation.1.bias']
     for i in range(spec.ddepth):
         names += block(f'decoder_blocks.{i}')
     names += ['final_layer.linear.weight', 'final_layer.linear.bias', 'final_layer.adaLN_modulation.1.weight',
@@ -139,8 +141,9 @@ class DiT(nn.Module):
     """Parameter container with the reference DiT's names, shapes, init distributions
     (models/maskdit.py:242-409) and the attributes the reference callers read
     (`patch_size`, `out_channels`, `extras`, `cls_token`, `mask_token`: train.py:138,
-    train_utils/loss.py:47,57,89).  Supported flag set = the shipped configs: use_decoder,
-    no cls token, no external features, no learn_sigma."""
+    train_utils/loss.py:47,57,89).  Supported flag set = the shipped configs, with or without the decoder
+    (use_decoder): no cls token, no external features, no learn_sigma.  Without the decoder
+    `decoder_pos_embed`, `decoder_layer`, `decoder_blocks` and `mask_token` are None, as in the reference."""
 
     def __init__(self, spec: Spec):
         super().__init__()
@@ -152,7 +155,7 @@ class DiT(nn.Module):
         self.extras = 0
         self.decoder_extras = 0
         self.cls_token = None
-        self.use_decoder = True
+        self.use_decoder = spec.use_decoder
         self.use_encoder_feat = False
         from .engine import param_table
         T, D, Dd = spec.T, spec.D, spec.Dd
@@ -163,12 +166,16 @@ class DiT(nn.Module):
         # (train.py:141 hands `model.parameters()` to FusedAdam, :153/:264 save / load its state by index).  The
         # ARENA order (engine.param_table) is independent of it.
         shapes = {name[len('model.'):]: shp for name, shp in param_table(spec)}
-        shapes['pos_embed'], shapes['decoder_pos_embed'] = (1, T, D), (1, T, Dd)
+        shapes['pos_embed'] = (1, T, D)
+        if spec.use_decoder:
+            shapes['decoder_pos_embed'] = (1, T, Dd)
         for name in reference_param_order(spec):
             _attach(self, name, nn.Parameter(torch.zeros(shapes.pop(name)), requires_grad=name not in ('pos_embed', 'decoder_pos_embed')))
         assert not shapes, f'parameters missing from the registration order: {sorted(shapes)}'
-        if not spec.mae:
+        if not (spec.mae and spec.use_decoder):
             self.mask_token = None
+        if not spec.use_decoder:
+            self.decoder_pos_embed = self.decoder_layer = self.decoder_blocks = None
         self.initialize_weights()
 
     @torch.no_grad()
@@ -190,7 +197,8 @@ class DiT(nn.Module):
                 p.uniform_(-a, a)
         g = int(sp.T ** 0.5)
         self.pos_embed.copy_(sincos_pos_embed(sp.D, g).unsqueeze(0))
-        self.decoder_pos_embed.copy_(sincos_pos_embed(sp.Dd, g).unsqueeze(0))
+        if self.decoder_pos_embed is not None:
+            self.decoder_pos_embed.copy_(sincos_pos_embed(sp.Dd, g).unsqueeze(0))
 
 
 class EDMPrecond(nn.Module):
@@ -321,6 +329,8 @@ class EDMPrecond(nn.Module):
         evaluation with mask_ratio > 0 then raises NotImplementedError."""
         if precision not in TRAIN_PRECISIONS:
             raise ValueError(f"train precision must be one of {', '.join(map(repr, TRAIN_PRECISIONS))}, got {precision!r}")
+        if precision == 'fp32' and not self.spec.use_decoder:
+            raise NotImplementedError(NODECODER_FP32_MESSAGE)
         self.train_precision = precision
         return self
 
@@ -328,6 +338,8 @@ class EDMPrecond(nn.Module):
         """Plan precision of a training evaluation; refuses what the fp32 route does not cover."""
         if self.train_precision != 'fp32':
             return 'bf16'
+        if not self.spec.use_decoder:
+            raise NotImplementedError(NODECODER_FP32_MESSAGE)
         if masked:
             raise NotImplementedError(MASKED_FP32_MESSAGE)
         return 'fp32'
