@@ -265,6 +265,47 @@ int mdt_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema,
                        float lr, float beta1, float beta2, float eps, float weight_decay, float bc1,
                        float bc2, float ema_decay, float grad_scale, mdt_stream_t stream);
 int mdt_ema_update(float* ema, const float* p, long n, float decay, mdt_stream_t stream);
+
+/* Guard around the optimizer step: what the reference's GradScaler did for it (train.py:39-50,226: a backward with an
+ * inf / NaN leaves optimizer.step() unexecuted) plus torch.nn.utils.clip_grad_norm_, decided on the device.  One record
+ * per optimizer (64 bytes, 16-byte aligned, zero-initialised by the caller):
+ *   sumsq, nonfinite  ordered fp64 sum of g^2 over the ranges summed so far / whether a sum was inf or NaN.  Both are
+ *                     doubles so that a sharded optimizer all-reduces them as one pair between sum and decision;
+ *   grad_scale        factor of the last mdt_grad_sumsq (norm = grad_scale * sqrt(sumsq));
+ *   norm, coef, skip  written by mdt_guard_decide: pre-clip norm, min(1, max_norm / (norm + 1e-6)), skip decision;
+ *   applied, skipped  step counters; inv_bc1 / inv_sqrt_bc2 = Adam's bias corrections of `applied`. */
+typedef struct mdt_guard_state {
+  double sumsq;
+  double nonfinite;
+  float norm;
+  float coef;
+  int32_t skip;
+  float grad_scale;
+  int64_t applied;
+  int64_t skipped;
+  float inv_bc1;
+  float inv_sqrt_bc2;
+  int32_t reserved[2];
+} mdt_guard_state;
+/* state->sumsq (+)= sum of g[i]^2, i < n, in fp64 and in a fixed order: workgroup c sums the chunk
+ * [c * chunk, (c + 1) * chunk) with chunk = mdt_grad_sumsq_chunk(n) -- a function of n alone -- into ws[c] (fp64), one
+ * workgroup then adds the partials in index order.  No atomics: two launches give the same bits.  accumulate != 0 adds
+ * onto the record (several ranges, one norm).  ws: mdt_grad_sumsq_ws_floats(n) floats, 16-byte aligned like g. */
+long mdt_grad_sumsq_chunk(long n);
+long mdt_grad_sumsq_ws_floats(long n);
+int mdt_grad_sumsq(const float* g, long n, float grad_scale, float* ws, long ws_floats, mdt_guard_state* state,
+                   int accumulate, mdt_stream_t stream);
+/* One thread: norm = grad_scale * sqrt(sumsq); skip = skip_nonfinite && non-finite; coef as above (max_norm 0 = 1);
+ * `applied` advances (and the bias corrections 1 - beta^applied follow) unless skipped, `skipped` otherwise.  A launch
+ * of its own so that (sumsq, nonfinite) can be all-reduced first. */
+int mdt_guard_decide(mdt_guard_state* state, float max_norm, int skip_nonfinite, double beta1, double beta2,
+                     mdt_stream_t stream);
+/* mdt_adamw_ema_step with grad_scale * state->coef; on state->skip only ema = d * ema + (1 - d) * p runs and p, m, v
+ * and w16 are not written.  device_bc != 0: bias corrections from the record (bc1 / bc2 are ignored). */
+int mdt_adamw_ema_step_guarded(float* p, const float* g, float* m, float* v, float* ema, mdt_bf16* w16, long n,
+                               float lr, float beta1, float beta2, float eps, float weight_decay, float bc1,
+                               float bc2, float ema_decay, float grad_scale, const mdt_guard_state* state,
+                               int device_bc, mdt_stream_t stream);
 /* batched [rows, cols] -> [cols, rows] bf16 transposes inside one arena; table = int64
  * (src_off, dst_off, rows, cols, tile_start) x n_entries (device), total_tiles over 64x64 tiles. */
 int mdt_transpose_bf16_batched(const mdt_bf16* src, mdt_bf16* dst, const int64_t* table, int n_entries,

@@ -89,6 +89,9 @@ _PROTOS = {
     'mdt_class_dropout': [vp, vp, f32, i32, i32],
     'mdt_adamw_ema_step': [vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, f32],
     'mdt_ema_update': [vp, vp, i64, f32],
+    'mdt_grad_sumsq': [vp, i64, f32, vp, i64, vp, i32],
+    'mdt_guard_decide': [vp, f32, i32, C.c_double, C.c_double],
+    'mdt_adamw_ema_step_guarded': [vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp, i32],
     'mdt_transpose_bf16_batched': [vp, vp, vp, i32, i32],
     'mdt_sampler_prep': [vp, vp, vp, i32, vp, vp, i32, i32, i32, f32],
     'mdt_sampler_euler': [vp, vp, vp, vp, f32, i32, vp, vp, i32, i32, f32],
@@ -148,6 +151,8 @@ _PLAIN = {
     'mdt_gemm_f32_tn_ws_floats': [i32, i32, i32, i32],
     'mdt_colsum_f32_ws_floats': [i32, i32],
     'mdt_attn_f32_bwd_ws_floats': [i32, i32, i32, i32],
+    'mdt_grad_sumsq_chunk': [i64],
+    'mdt_grad_sumsq_ws_floats': [i64],
 }
 EXPORTED = sorted(list(_PROTOS) + list(_PLAIN) + ['mdt_last_error', 'mdt_version'])
 ABI_VERSION = 4  # == MDT_ABI_VERSION of include/maskdit_hip.h (tests/test_capi_cpu.py compares the two)
@@ -212,7 +217,7 @@ def lib():
     for name, argt in _PLAIN.items():
         fn = getattr(L, name)
         fn.argtypes = argt
-        fn.restype = i64 if name.endswith('_ws_floats') else i32
+        fn.restype = i64 if name.endswith(('_ws_floats', '_chunk')) else i32
     L.mdt_last_error.restype = C.c_char_p
     L.mdt_last_error.argtypes = []
     L.mdt_version.restype = i32

@@ -6,9 +6,13 @@ case: `FusedAdam(model.parameters(), ...)`), `step()` is ONE streaming HIP kerne
 arenas -- p, g, exp_avg, exp_avg_sq (+ the EMA arena when `fuse_ema` was called, + the bf16
 GEMM-operand shadow) -- followed by the batched transposes that refresh the K-major shadows.
 Otherwise it runs the same kernel per tensor.  There is no torch-eager fallback.
+
+`FusedAdam(..., max_grad_norm=..., skip_nonfinite=True)` puts the device-side guard of maskdit_amd/guard.py around the
+step: sum of squares of the gradient -> decision -> guarded kernel.  With both off nothing changes.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -31,17 +35,34 @@ def _st():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _check_max_grad_norm(max_grad_norm) -> float:
+    """None / 0 / False = no clipping (0.0); a negative or non-finite value is an error."""
+    if max_grad_norm is None or max_grad_norm is False:
+        return 0.0
+    v = float(max_grad_norm)
+    if not math.isfinite(v) or v < 0:
+        raise ValueError(f'max_grad_norm must be a finite number >= 0 (None / 0 = no clipping), got {max_grad_norm!r}')
+    return v
+
+
 class FusedAdam(torch.optim.Optimizer):
     """API of apex.optimizers.FusedAdam as the reference uses it: constructor keywords
     (`lr`, `betas`, `eps`, `adam_w_mode`, `weight_decay`, `bias_correction`), writable
     `param_groups[i]['lr']` (train.py:224-225), `step()`, `state_dict()/load_state_dict()`
     (train.py:153-157,264).  State layout follows apex: `group['step']` plus per-parameter
-    `exp_avg` / `exp_avg_sq` (here: views into two flat moment arenas)."""
+    `exp_avg` / `exp_avg_sq` (here: views into two flat moment arenas).
+
+    Beyond apex: `max_grad_norm` (clip the gradient to this global L2 norm, torch's clip_grad_norm_ formula) and
+    `skip_nonfinite` (a step whose gradient holds an inf / NaN changes nothing but the EMA, as under the reference's
+    GradScaler).  Both are decided on the device (no host sync); `grad_norm` / `skipped_steps` report.  With
+    `skip_nonfinite`, `param_groups[i]['step']` counts APPLIED steps: the device owns the count, and `state_dict()` /
+    `skipped_steps` bring the host's copy up to date."""
 
     def __init__(self, params, lr=1e-3, bias_correction=True, betas=(0.9, 0.999), eps=1e-8, adam_w_mode=True,
-                 weight_decay=0.0, amsgrad=False, set_grad_none=True):
+                 weight_decay=0.0, amsgrad=False, set_grad_none=True, max_grad_norm=None, skip_nonfinite=False):
         if amsgrad:
             raise RuntimeError('FusedAdam does not support the AMSGrad variant.')
+        max_norm = _check_max_grad_norm(max_grad_norm)
         defaults = dict(lr=lr, bias_correction=bias_correction, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         if not adam_w_mode and weight_decay != 0:
@@ -52,6 +73,12 @@ class FusedAdam(torch.optim.Optimizer):
         self._ema = None  # (ema_model, decay) when fuse_ema() was called
         self._arena: Optional[Engine] = None
         self._m = self._v = None
+        self._guard = None  # maskdit_amd.guard.GuardState when clipping / skipping is on (created at the first step)
+        self._guard_cfg = (max_norm, bool(skip_nonfinite)) if (max_norm > 0 or skip_nonfinite) else None
+        if skip_nonfinite and any((g['betas'], g['bias_correction']) != (self.param_groups[0]['betas'], self.param_groups[0]['bias_correction'])
+                                  for g in self.param_groups):
+            raise ValueError('skip_nonfinite: the device keeps ONE applied-step count and its bias corrections, so every '
+                             'parameter group needs the same betas and bias_correction')
         self._resolve_arena()
 
     # ---- layout ---------------------------------------------------------------------------
@@ -106,6 +133,8 @@ class FusedAdam(torch.optim.Optimizer):
                 loss = closure()
         if self._arena is not None and _engine_of(self._first) is not self._arena:
             self._resolve_arena()  # the module was moved / re-bound
+        if self._guard_cfg is not None and not self._guard_decide():
+            return loss  # no gradient anywhere: nothing to decide, nothing to step
         for group in self.param_groups:
             group['step'] = group.get('step', 0) + 1
             t = group['step']
@@ -126,6 +155,79 @@ class FusedAdam(torch.optim.Optimizer):
             else:
                 self._step_tensors(group, hyp)
         return loss
+
+    # ---- guard (max_grad_norm / skip_nonfinite) ---------------------------------------------
+    def _grad_ranges(self):
+        """(device pointer, elements, keep-alive) of every gradient range this step will consume."""
+        if self._arena is not None:
+            n_none = sum(1 for p in self._trainable if p.grad is None)
+            if n_none == 0:
+                G = self._arena.G
+                return [] if G is None else [(G.data_ptr(), self._arena.lay.n, G)]
+        out = []
+        for group in self.param_groups:
+            for p in group['params']:
+                if p.grad is not None:
+                    if not p.grad.is_cuda or p.grad.dtype != torch.float32:
+                        raise _lib.MaskDiTLibError('FusedAdam: gradients must be fp32 tensors on a HIP device')
+                    g = p.grad.contiguous()
+                    out.append((g.data_ptr(), g.numel(), g))
+        return out
+
+    def _guard_reduce(self, guard):
+        """Between sum and decision (ShardedFusedAdam: all-reduce of the (sum, flag) pair)."""
+
+    def _guard_decide(self) -> bool:
+        """sumsq over this step's gradient ranges -> decide.  False when there is no gradient at all."""
+        ranges = self._grad_ranges()
+        if not ranges:
+            return False
+        if self._guard is None:
+            from .guard import GuardState
+            self._guard = GuardState(ranges[0][2].device, *self._guard_cfg)
+            if self._guard.skip_nonfinite:
+                self._guard.set_applied(self.param_groups[0].get('step', 0))
+        guard = self._guard
+        guard.begin()
+        for ptr, n, _keep in ranges:
+            guard.sumsq(ptr, n, self.grad_scale, _st())
+        self._guard_reduce(guard)
+        g0 = self.param_groups[0]
+        b1, b2 = g0['betas'] if g0['bias_correction'] else (0.0, 0.0)  # (1 - 0^t = 1: no correction)
+        guard.decide(b1, b2, _st())
+        return True
+
+    def _adamw(self, p, g, m, v, ema, w16, n, hyp, decay):
+        """The step kernel over one range: the plain entry, or the guarded one when a guard is on."""
+        if self._guard is None:
+            call('mdt_adamw_ema_step', p, g, m, v, ema, w16, n, *hyp, decay, float(self.grad_scale), _st())
+        else:
+            self._guard.step(p, g, m, v, ema, w16, n, hyp, decay, self.grad_scale, _st())
+
+    @property
+    def grad_norm(self):
+        """Pre-clip gradient norm of the last step(): a 0-dim DEVICE tensor (reading it is the caller's sync); None
+        without a guard or before the first step."""
+        return None if self._guard is None else self._guard.norm
+
+    def _refresh_step(self):
+        """With skip_nonfinite the device owns the applied-step count: copy it into the parameter groups (syncs)."""
+        if self._guard is not None and self._guard.skip_nonfinite:
+            t = self._guard.applied_steps()
+            for group in self.param_groups:
+                group['step'] = t
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps the guard skipped so far (syncs; also refreshes param_groups[i]['step'])."""
+        if self._guard is None:
+            return 0
+        self._refresh_step()
+        return self._guard.skipped_steps()
+
+    def state_dict(self):
+        self._refresh_step()
+        return super().state_dict()
 
     def _step_mixed(self, group, hyp):
         """Some (not all) gradients of an arena-bound model are None: per-tensor kernels on the parameters that have one."""
@@ -151,16 +253,14 @@ class FusedAdam(torch.optim.Optimizer):
             if ema_eng.lay.n != eng.lay.n:
                 raise ValueError('fuse_ema: EMA model layout differs from the trained model')
             ema_ptr, decay = ema_eng.P.data_ptr(), self._ema[1]
-        lr, b1, b2, eps, wd, bc1, bc2 = hyp
-        call('mdt_adamw_ema_step', eng.P.data_ptr(), G.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), ema_ptr,
-             eng.W16.data_ptr(), eng.lay.n, lr, b1, b2, eps, wd, bc1, bc2, decay, float(self.grad_scale), _st())
+        self._adamw(eng.P.data_ptr(), G.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), ema_ptr, eng.W16.data_ptr(), eng.lay.n,
+                    hyp, decay)
         eng.refresh_shadows(cast=False)  # K-major transposes + padded label table from the fresh bf16 shadow
         if self._ema is not None:
             ema_eng.shadows_dirty = True
             eng.ema_applied = (id(ema_eng), decay)
 
     def _step_tensors(self, group, hyp):
-        lr, b1, b2, eps, wd, bc1, bc2 = hyp
         touched = set()
         for p in group['params']:
             if p.grad is None:
@@ -172,8 +272,8 @@ class FusedAdam(torch.optim.Optimizer):
                 st['exp_avg'] = torch.zeros_like(p)
                 st['exp_avg_sq'] = torch.zeros_like(p)
             g = p.grad.contiguous()
-            call('mdt_adamw_ema_step', p.data_ptr(), g.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), None,
-                 None, p.numel(), lr, b1, b2, eps, wd, bc1, bc2, 0.0, float(self.grad_scale), _st())
+            self._adamw(p.data_ptr(), g.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), None, None, p.numel(),
+                        hyp, 0.0)
             eng = _engine_of(p)
             if eng is not None:
                 touched.add(eng)
@@ -204,6 +304,8 @@ class FusedAdam(torch.optim.Optimizer):
                         st[key].copy_(src[key])
                     if 'step' in src and 'step' not in g_new:  # torch.optim.AdamW-style checkpoint
                         g['step'] = int(src['step'])
+        if self._guard is not None and self._guard.skip_nonfinite:
+            self._guard.set_applied(self.param_groups[0].get('step', 0))  # (a guard created later starts from the group's count)
 
 
 @torch.no_grad()

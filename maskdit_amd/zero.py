@@ -26,7 +26,6 @@ from typing import List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from ._lib import call
 from .ddp import _global_rank, slab_pieces
 from .optim import FusedAdam, _st
 
@@ -85,6 +84,21 @@ class ShardedFusedAdam(FusedAdam):
         raise NotImplementedError('ShardedFusedAdam: every trainable parameter needs a gradient (the moments are sharded by '
                                   'arena range, not by tensor); some .grad are None')
 
+    # ---- guard: the norm of the whole gradient from the owned pieces ------------------------------
+    def _grad_ranges(self):
+        G = self._arena.G
+        if G is None:
+            return []
+        if any(p.grad is None for p in self._trainable):
+            self._step_mixed(None, None)  # refuses, exactly as the unguarded step does
+        return [(G.data_ptr() + 4 * a, e - a, G) for a, e in self._pieces]
+
+    def _guard_reduce(self, guard):
+        """ONE all-reduce of the record's (sum of squares, non-finite flag) pair: every rank then takes the same decision,
+        so the collective sequence of the step never diverges."""
+        if self.world > 1:
+            dist.all_reduce(guard.sum_flag, op=dist.ReduceOp.SUM, group=self.pg)
+
     def _step_arena(self, hyp):
         eng = self._arena
         G = eng.G
@@ -96,11 +110,9 @@ class ShardedFusedAdam(FusedAdam):
             if ema_eng.lay.n != eng.lay.n:
                 raise ValueError('fuse_ema: EMA model layout differs from the trained model')
             ema_base, decay = ema_eng.P.data_ptr(), self._ema[1]
-        lr, b1, b2, eps, wd, bc1, bc2 = hyp
         for (a, e), mo in zip(self._pieces, self._moff):  # one launch per owned piece (one per slab: ~45 on XL/2)
-            call('mdt_adamw_ema_step', eng.P.data_ptr() + 4 * a, G.data_ptr() + 4 * a, self._m.data_ptr() + 4 * mo,
-                 self._v.data_ptr() + 4 * mo, (ema_base + 4 * a) if ema_base else None, None, e - a, lr, b1, b2, eps, wd, bc1, bc2,
-                 decay, float(self.grad_scale), _st())
+            self._adamw(eng.P.data_ptr() + 4 * a, G.data_ptr() + 4 * a, self._m.data_ptr() + 4 * mo, self._v.data_ptr() + 4 * mo,
+                        (ema_base + 4 * a) if ema_base else None, None, e - a, hyp, decay)
         self._gather(eng.P, eng.lay.slabs)
         eng.refresh_shadows(cast=True)  # bf16 shadow of the gathered pieces + K-major transposes + label table
         self._consolidated = None
@@ -146,6 +158,7 @@ class ShardedFusedAdam(FusedAdam):
         """COLLECTIVE (every rank): gather the sharded moments into full arenas and bring the EMA up to date, so that
         `state_dict()` / `ema.state_dict()` can afterwards be called by rank 0 alone."""
         eng = self._arena
+        self._refresh_step()  # (skip_nonfinite: the applied-step count lives on the device, identical on every rank)
         full_m = torch.zeros(eng.lay.n, device=eng.P.device, dtype=torch.float32)
         full_v = torch.zeros_like(full_m)
         self._scatter_into(full_m, self._m)
@@ -157,6 +170,7 @@ class ShardedFusedAdam(FusedAdam):
 
     def state_dict(self):
         eng = self._arena
+        self._refresh_step()
         if self.world > 1:
             if self._consolidated is None or self._consolidated[0] != self.param_groups[0].get('step', 0):
                 raise RuntimeError('ShardedFusedAdam.state_dict(): the optimizer state is sharded over the ranks -- call '

@@ -230,7 +230,30 @@ def parse(argv=None):
     # which covers that unmasked stage: resolve_train_precision refuses a config whose mask-ratio schedule is ever > 0.
     ap.add_argument('--no_amp', action='store_true',
                     help='fp32 training (forward and backward in exact fp32) of the unmasked stage: needs mask_ratio 0')
+    # guard of the optimizer step (maskdit_amd/guard.py): the reference's fp16 run skipped optimizer.step() after a backward
+    # with an inf / NaN (GradScaler, train.py:39-50,226); bf16 / fp32 training has no scaler, so the guard is explicit here.
+    # Both default to the config keys train.max_grad_norm / train.skip_nonfinite, which default to off.
+    ap.add_argument('--max_grad_norm', type=float, default=None,
+                    help='clip the gradient to this global L2 norm inside the optimizer step (0 = off; default: train.max_grad_norm)')
+    ap.add_argument('--skip_nonfinite', type=str2bool, nargs='?', const=True, default=None,
+                    help='skip an optimizer step whose gradient holds an inf / NaN (default: train.skip_nonfinite)')
     return ap.parse_args(argv)
+
+
+def resolve_guard(args, cfg) -> dict:
+    """FusedAdam keywords of the step guard: the flags override the config keys; {} when both are off."""
+    tc = cfg.train
+    mx = getattr(args, 'max_grad_norm', None)
+    mx = tc.get('max_grad_norm', None) if mx is None else mx
+    sk = getattr(args, 'skip_nonfinite', None)
+    sk = tc.get('skip_nonfinite', False) if sk is None else sk
+    sk = str2bool(sk) if isinstance(sk, str) else bool(sk)
+    kw = {}
+    if mx:
+        kw['max_grad_norm'] = float(mx)
+    if sk:
+        kw['skip_nonfinite'] = True
+    return kw
 
 
 def mask_ratio_max(cfg) -> float:
@@ -357,10 +380,11 @@ def _train_loop(args, state):
     wire = str(tc.get('grad_wire', 'fp32')).lower()
     model = M.DataParallel(net, grad_wire_dtype=torch.bfloat16 if wire in ('bf16', 'bfloat16') else None) if world > 1 else net
     zero1 = bool(tc.get('zero1', False)) and world > 1
+    guard = resolve_guard(args, cfg)
     if zero1:  # optimizer state / optimizer + EMA stream sharded over the ranks (maskdit_amd/zero.py)
-        opt = M.ShardedFusedAdam(net.parameters(), data_parallel=model, lr=tc.lr, adam_w_mode=True, weight_decay=0)
+        opt = M.ShardedFusedAdam(net.parameters(), data_parallel=model, lr=tc.lr, adam_w_mode=True, weight_decay=0, **guard)
     else:
-        opt = M.FusedAdam(net.parameters(), lr=tc.lr, adam_w_mode=True, weight_decay=0)
+        opt = M.FusedAdam(net.parameters(), lr=tc.lr, adam_w_mode=True, weight_decay=0, **guard)
     step0 = 0
     if args.ckpt_path:  # train.py:147-162
         if world > 1:
@@ -391,7 +415,8 @@ def _train_loop(args, state):
     if rank == 0:
         print(f'{mc.model_type} params {sum(p.numel() for p in net.parameters()):,}  global batch {global_batch} '
               f'({world} GPU x {mb} x accum {accum})  steps {step0} -> {step0 + max_steps}'
-              + ('  [ZeRO-1]' if zero1 else '') + (f'  [gradient wire {wire}]' if world > 1 else ''), flush=True)
+              + ('  [ZeRO-1]' if zero1 else '') + (f'  [gradient wire {wire}]' if world > 1 else '')
+              + (f'  [step guard {guard}]' if guard else ''), flush=True)
         if train_precision == 'fp32':
             print('--no_amp: exact fp32 forward and backward from the fp32 master weights (unmasked stage)'
                   + (f'; train.tf32={tc.tf32} is read and ignored: there is no TF32 on this device, and fp32 is the tighter '
@@ -399,7 +424,7 @@ def _train_loop(args, state):
 
     batches = make_batches(cfg, args, dev, rank, world, mb * accum)
     step, log_steps, running = step0, 0, torch.zeros((), device=dev)
-    last_loss = last_eval = None
+    last_loss = last_eval = last_norm = last_skipped = None
     t0 = time.time()
     for mom, cls in batches:
         x = M.sample(mom)                                      # train.py:203
@@ -435,9 +460,13 @@ def _train_loop(args, state):
                 dist.all_reduce(avg, op=dist.ReduceOp.SUM)
                 avg = avg / world
             last_loss = avg.item()
+            guard_log = ''
+            if guard:  # read at the sync this log line already performs
+                last_norm, last_skipped = (opt.grad_norm.item() if opt.grad_norm is not None else None), opt.skipped_steps
+                guard_log = f', Grad Norm: {last_norm if last_norm is not None else float("nan"):.4f}, Skipped: {last_skipped}'
             if rank == 0:
                 print(f'(step={step:07d}) Train Loss: {last_loss:.4f}, Train Steps/Sec: {sps:.2f}, '
-                      f'img/s: {sps * global_batch:.1f}, mem: {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB', flush=True)
+                      f'img/s: {sps * global_batch:.1f}, mem: {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB{guard_log}', flush=True)
             running.zero_()
             log_steps, t0 = 0, time.time()
         if step % cfg.log.ckpt_every == 0 and step > step0:            # train.py:259-271
@@ -463,7 +492,10 @@ def _train_loop(args, state):
         dist.barrier()
     if zero1:
         opt.sync_ema()
-    return {'net': net, 'ema': ema, 'opt': opt, 'step': step, 'loss': last_loss, 'exp_dir': exp_dir, 'eval': last_eval}
+    out = {'net': net, 'ema': ema, 'opt': opt, 'step': step, 'loss': last_loss, 'exp_dir': exp_dir, 'eval': last_eval}
+    if guard:
+        out['grad_norm'], out['skipped'] = last_norm, last_skipped
+    return out
 
 
 def main():
